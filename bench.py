@@ -8,23 +8,41 @@ path) over the whole per-GPU batch of synthetic 64-byte slots already
 resident in HBM.
 
   python bench.py [--gpus N] [--steps K] [--warmup W] [--config c2|c1|c3|c4|c5|l2]
-                  [--extra c1,c3,c5|none] [--algo auto|linear|indexed|hybrid]
+                  [--algo auto|linear|indexed|hybrid] [--dump-outputs DIR]
+                  [--full [--extra c1,c3,c5|none] ...]
 
-At N = 1 the same process then measures the other single-GPU BASELINE.json
-configs named by --extra (default C1: examples/firewall's firewall.conf, C3:
+A plain run sets up, does W untimed launches, times K launches, writes the
+last launch's verdicts if --dump-outputs is given and prints the one JSON
+line: the headline with its config and roofline (from the timed region's own
+HIP events).  Everything below that is not the headline runs only with --full:
+the oracle spot check, the per-launch spread pass, the CPU baselines, the
+PCIe-inclusive rate, the device group, the call shapes, the further configs,
+the N > 1 root-scattered leg and the "summary" block; --full exits 1 if any of
+its checks is not bit-exact.
+
+--dump-outputs DIR writes what the last timed launch left in the caller's
+buffers: DIR/port.npy (float64, L3ACLPort per packet; a fixed seeded sample of
+2^22 packets when the batch is larger) and DIR/permit_bits.npy (float64
+[words, 2]: low and high 32 bits of every 64-packet permit word; sampled the
+same way above 2^20 words).  Rules and packets come from fixed seeds, so two
+builds can be compared output for output.
+
+With --full at N = 1 the same process then measures the other single-GPU
+BASELINE.json configs named by --extra (default C1: examples/firewall's firewall.conf, C3:
 10 k rules on IMIX frames, C5: 100 k rules with port ranges — the "LDS
 rule-table tiling stress") and reports them under "configs", each with its
 own metric, roofline and CPU baseline; `value` stays the C2 headline.
 
-Key order of the one JSON line: the contract's keys, "configs", the compact
+Key order of the --full JSON line: the contract's keys, "configs", the compact
 "call_shapes", the PCIe-inclusive rate, and last a "summary" of every headline
-figure, so that a reader who keeps only the line's tail still has them all.  (`--config l2` measures the L2 ACL kernel, SURVEY.md
-§8f row 4 — not a BASELINE.json config.)
+figure, so that a reader who keeps only the line's tail still has them all.
+(`--config l2` measures the L2 ACL kernel, SURVEY.md §8f row 4 — not a
+BASELINE.json config.)
 
 N > 1 runs under torch.distributed.run (one rank per GPU, RCCL): rank 0
 generates the rule file and broadcasts its bytes over RCCL (the path's one real
 exchange step, outside the timed region); every rank classifies its own
-resident shard — no data-path collective ("scaling": "weak").  The
+resident shard — no data-path collective ("scaling": "weak").  With --full the
 root-scattered deployment (dist.scatter of slots / dist.gather of verdicts)
 is reported beside it as "scatter_inclusive".
 
@@ -34,6 +52,7 @@ Every JSON record carries:
                4 B) x packets per launch / mean kernel time
                (HIP events on the launch stream); peak = 8 TB/s HBM3E;
                traffic = PMC bytes per launch from profiles/ (if collected)
+and with --full:
   cpu_baseline the oracle (oracle/acl_oracle.c, the reference algorithm
                restated in C) on a bounded sample of the same packets, on
                this host's cores: the GPU box's CPU share (<= 16 threads,
@@ -202,6 +221,27 @@ def cpu_leg(run, n: int, budget_s: float, what: str, all_budget_s: float = 2.0):
     return out, ports[:sample]
 
 
+DUMP_MAX_PACKETS = 1 << 22  # float64 verdicts: 32 MiB, + at most 2^20 permit words (16 MiB; 4 MiB at the default batch)
+DUMP_SEED = 20240229
+
+
+def dump_outputs(path: str, port, permit, n: int):
+    """--dump-outputs: the caller's port / permit buffers as the last timed
+    launch left them, as float64 (exact for u32 verdicts and 32-bit halves)."""
+    out = Path(path)
+    out.mkdir(parents=True, exist_ok=True)
+    def sample(a, limit):
+        if len(a) <= limit:
+            return a
+        return a[np.sort(np.random.default_rng(DUMP_SEED).choice(len(a), limit, replace=False))]
+
+    p = sample(port.cpu().numpy().view(np.uint32)[:n], DUMP_MAX_PACKETS)
+    w = sample(permit.cpu().numpy().view(np.uint64)[: (n + 63) // 64], DUMP_MAX_PACKETS // 4)
+    np.save(out / "port.npy", p.astype(np.float64))
+    np.save(out / "permit_bits.npy",
+            np.stack([w & np.uint64(0xFFFFFFFF), w >> np.uint64(32)], axis=1).astype(np.float64))
+
+
 def run_config(cfg: str, args, rank: int, world: int, local: int, dev, nd, headline: bool):
     """Measure one config on this rank: returns (record dict, state for the
     headline's extra legs)."""
@@ -209,7 +249,8 @@ def run_config(cfg: str, args, rank: int, world: int, local: int, dev, nd, headl
     import torch.distributed as dist
     import nffacl
     from nffacl import synth
-    from oracle import oracle, rules_oracle as ro
+    if args.full:
+        from oracle import oracle, rules_oracle as ro
 
     n = args.packets
     algo_id = {"auto": nffacl.ALGO_AUTO, "linear": nffacl.ALGO_LINEAR, "indexed": nffacl.ALGO_INDEXED,
@@ -283,37 +324,42 @@ def run_config(cfg: str, args, rank: int, world: int, local: int, dev, nd, headl
     if world > 1:
         dist.barrier()
     elapsed = time.perf_counter() - t_start
+    if headline and rank == 0 and args.dump_outputs:
+        dump_outputs(args.dump_outputs, port, permit, n)
     if args.timing == "region":  # mean launch duration over the region, gaps included
         kms = np.full(args.steps, evs[0][0].elapsed_time(evs[0][1]) / args.steps)
-        # per-launch spread (min/p50/max) from a separate, untimed pass with an
-        # event pair around each launch; the region mean stays the roofline basis
-        m = min(args.steps, 20)
-        for s in range(m):
-            evs[s][0].record(stream)
-            launch()
-            evs[s][1].record(stream)
-        torch.cuda.synchronize(dev)
-        spread = np.array([a.elapsed_time(b) for a, b in evs[:m]])
+        spread = kms
+        if args.full:
+            # per-launch spread (min/p50/max) from a separate, untimed pass with an
+            # event pair around each launch; the region mean stays the roofline basis
+            m = min(args.steps, 20)
+            for s in range(m):
+                evs[s][0].record(stream)
+                launch()
+                evs[s][1].record(stream)
+            torch.cuda.synchronize(dev)
+            spread = np.array([a.elapsed_time(b) for a, b in evs[:m]])
     else:
         kms = np.array([a.elapsed_time(b) for a, b in evs])  # per-launch kernel time (ms)
         spread = kms
     elapsed = nd.max_over_ranks(elapsed, dev)
 
-    # ---- spot parity check (outside timing): GPU verdicts vs oracle sample ----
-    got = port.cpu().numpy().view(np.uint32)
-    rng = np.random.default_rng(rank)
-    idx = np.sort(rng.choice(n, min(n, 4096), replace=False))
-    eth = a4 = a6 = None
-    if l2_mode:
-        eth = ro.parse_l2_text_table(text.encode()).array()
-        want = oracle.l2_classify_slots(slots.reshape(n, 64)[idx].reshape(-1), 64, len(idx), eth, threads=4)
-    else:
-        a4, a6 = ro.parse_text_table(text.encode()).arrays()
-        if frames_mode:
-            want = oracle.classify_frames(frames, desc[idx], a4, a6, threads=4)
+    # ---- spot parity check (--full, outside timing): GPU verdicts vs oracle sample ----
+    got = idx = eth = a4 = a6 = None
+    if args.full:
+        got = port.cpu().numpy().view(np.uint32)
+        rng = np.random.default_rng(rank)
+        idx = np.sort(rng.choice(n, min(n, 4096), replace=False))
+        if l2_mode:
+            eth = ro.parse_l2_text_table(text.encode()).array()
+            want = oracle.l2_classify_slots(slots.reshape(n, 64)[idx].reshape(-1), 64, len(idx), eth, threads=4)
         else:
-            want = oracle.classify_slots(slots.reshape(n, 64)[idx].reshape(-1), 64, len(idx), a4, a6, threads=4)
-    bit_exact = bool((got[idx] == want).all())
+            a4, a6 = ro.parse_text_table(text.encode()).arrays()
+            if frames_mode:
+                want = oracle.classify_frames(frames, desc[idx], a4, a6, threads=4)
+            else:
+                want = oracle.classify_slots(slots.reshape(n, 64)[idx].reshape(-1), 64, len(idx), a4, a6, threads=4)
+        bit_exact = bool((got[idx] == want).all())
 
     total = n * world * args.steps
     value = total / elapsed / 1e6
@@ -344,8 +390,9 @@ def run_config(cfg: str, args, rank: int, world: int, local: int, dev, nd, headl
             "kernel_ms_p50": round(float(np.median(spread)), 5), "kernel_ms_max": round(float(spread.max()), 5),
             "timing": args.timing,
         },
-        "bit_exact_sample": bit_exact,
     }
+    if args.full:
+        rec["bit_exact_sample"] = bit_exact
     state = dict(eng=eng, n=n, port=port, got=got, idx=idx, slots=slots, frames=frames, desc=desc,
                  d_slots=None if frames_mode else d_slots, a4=a4, a6=a6, eth=eth, stream=stream,
                  frames_mode=frames_mode, l2_mode=l2_mode)
@@ -577,7 +624,15 @@ def main():
                     help="N=1: skip the C-ABI device-group leg (nffacl_group_classify_device)")
     ap.add_argument("--backend", default="nccl", choices=["nccl", "gloo"],
                     help="process-group backend for N>1 (nccl = RCCL on ROCm)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run everything beside the headline: oracle checks, CPU baselines, PCIe-inclusive "
+                         "rate, device group, call shapes, the --extra configs, N>1 scatter leg, summary")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="write the last timed launch's verdicts as DIR/port.npy and DIR/permit_bits.npy")
     args = ap.parse_args()
+    if not args.full:  # a plain run: set up, warm up, time the K launches, print the headline
+        args.no_cpu_baseline = args.no_host = args.no_scatter = args.no_shapes = args.no_group = True
+        args.extra = "none"
 
     import torch
     import torch.distributed as dist
@@ -600,9 +655,11 @@ def main():
         "steps": args.steps, "warmup": args.warmup, "ms_per_step": rec["ms_per_step"],
         "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "u32",
         "data": "synthetic (deterministic seeds; SURVEY.md §8d mix)",
-        "config": rec["config"], "roofline": rec["roofline"], "bit_exact_sample": rec["bit_exact_sample"],
+        "config": rec["config"], "roofline": rec["roofline"],
     }
-    ok = rec["bit_exact_sample"]
+    ok = True
+    if args.full:
+        ok = out["bit_exact_sample"] = rec["bit_exact_sample"]
     eng, n, got, idx = st["eng"], st["n"], st["got"], st["idx"]
     host = {}
 
@@ -663,7 +720,7 @@ def main():
         cb["bit_exact_vs_gpu"] = bool((cports == got[: len(cports)]).all())
         out["cpu_baseline"] = cb
         ok = ok and cb["bit_exact_vs_gpu"]
-    elif rank == 0:
+    elif rank == 0 and args.full:
         out["cpu_baseline"] = None
     if rank == 0 and world == 1 and not args.no_group and not st["frames_mode"] and not st["l2_mode"]:
         out["device_group"] = group_leg(st, args, rec["ms_per_step"], text_of(cfg), local)
@@ -702,7 +759,8 @@ def main():
         out["call_shapes"] = {c: compact_shapes(v) for c, v in shapes.items()}
     out.update(host)
     if rank == 0:
-        out["summary"] = summary(out, ok, cfg)
+        if args.full:
+            out["summary"] = summary(out, ok, cfg)
         print(json.dumps(out, separators=(",", ":")), flush=True)
     if world > 1:
         dist.destroy_process_group()

@@ -7,7 +7,7 @@ for rep in $(seq $REPS); do for spec in "$@"; do
   name=${spec%%=*}; kv=${spec#*=}; envs=()
   IFS=, read -ra pairs <<< "$kv"
   for p in "${pairs[@]}"; do [ -n "$p" ] && envs+=("${p%%:*}=${p#*:}"); done
-  env "${envs[@]}" NFFACL_BENCH_SHAPES="$SH" timeout -k 10 300 python bench.py --config c2 --extra none --no-host \
+  env "${envs[@]}" NFFACL_BENCH_SHAPES="$SH" timeout -k 10 300 python bench.py --full --config c2 --extra none --no-host \
       --steps 5 --warmup 2 > "$OUT/${name}_$rep.json" 2> "$OUT/${name}_$rep.err" || { echo "$name failed"; tail -5 "$OUT/${name}_$rep.err"; exit 1; }
   python3 -c "
 import json,sys
