@@ -592,6 +592,53 @@ NFFACL_API void nffacl_group_destroy(nffacl_group *g);
  * i outside 0..N-1, n > 2^48 or NULL outputs. */
 NFFACL_API int nffacl_group_shard(uint64_t n, int n_devices, int i, uint64_t *off, uint64_t *len);
 
+/* ---- routing: per-output index lists of a classified batch ---------------
+ * SetSeparator / SetSplitter do not return verdicts, they route: the scalar
+ * loop of segmentProcess appends every packet of a burst to
+ * OutputMbufs[answer] in arrival order and enqueues one slice per output flow
+ * (flow/flow.go:1462-1486; the vector form through asm.GenerateMask,
+ * flow.go:1505-1517) — a stable partition of the burst by answer.  A router
+ * computes that partition for a verdict vector resident in HBM (the d_port of
+ * the classify calls above), entirely on the device.  Additive to ABI 7. */
+enum nffacl_route_mode {
+    NFFACL_ROUTE_SEPARATE = 0, /* n_out = 2, output = (port != 0): separate, flow.go:1795-1797 —
+                                  the rejected flow is output 0, the accepted flow output 1 */
+    NFFACL_ROUTE_SPLIT = 1     /* output = port, n_out = the splitter's flowNumber, 1..255
+                                  (makeSplitter(..., uint8(flowNumber)), flow.go:1161).  A port >=
+                                  n_out indexes next[] out of range in the reference (the Go
+                                  runtime panics); here such packets form one extra out-of-range
+                                  segment after the last output, and are counted. */
+};
+typedef struct nffacl_router nffacl_router;
+/* A router for batches of up to max_n (<= 2^31) packets on `hip_device`.  It
+ * owns its scratch (per-tile counts, sized by max_n here; launches allocate
+ * nothing, so they can be captured into a graph) and serves launches in
+ * stream order on one stream at a time: one router per stream. */
+NFFACL_API int nffacl_router_create(int hip_device, uint32_t mode, uint32_t n_out, uint64_t max_n,
+                                    nffacl_router **out);
+/* d_index[n] <- a permutation of 0..n-1: the indices of output 0's packets in
+ * ascending (arrival) order, then output 1's, ..., the out-of-range segment
+ * last — OutputMbufs[0], [1], ... of flow.go:1462-1486 laid end to end.
+ * d_offsets[n_out + 2]: [o] = start of output o's segment, [n_out] = start of
+ * the out-of-range segment, [n_out + 1] = n.  n = 0 writes only the offsets.
+ * Asynchronous on `stream` (three kernel launches; no workgroup waits on
+ * another).  NFFACL_ERR_INVALID_ARG for NULL pointers or n > max_n. */
+NFFACL_API int nffacl_route_device(nffacl_router *r, const uint32_t *d_port, uint64_t n, uint32_t *d_index,
+                                   uint32_t *d_offsets, void *stream);
+/* d_out slot j <- slot d_index[j] of d_slots, j < m (the packets of an output
+ * slice made dense, e.g. for a D2H of the permitted packets only; slots as
+ * nffacl_classify_device: stride % 16 == 0, stride >= 64, both buffers 16-byte
+ * aligned, else NFFACL_ERR_INVALID_ARG). */
+NFFACL_API int nffacl_route_gather_device(const uint8_t *d_slots, uint32_t stride, const uint32_t *d_index,
+                                          uint64_t m, uint8_t *d_out, void *stream);
+/* The router's plan (pure, no device): the tiles n packets are cut into and
+ * the scratch bytes a router of max_n = n holds, tiles * (n_out + 1) * 4.
+ * NFFACL_ERR_INVALID_ARG for n > 2^31, n_out outside 1..255 or NULL outputs. */
+NFFACL_API int nffacl_route_plan(uint64_t n, uint32_t n_out, uint64_t *tiles, uint64_t *scratch_bytes);
+/* Waits for the router's last launch (its own event, no device-wide
+ * synchronise), then frees. */
+NFFACL_API void nffacl_router_destroy(nffacl_router *r);
+
 /* ---- misc ------------------------------------------------------------- */
 NFFACL_API const char *nffacl_strerror(int status);
 NFFACL_API int nffacl_abi_version(void);

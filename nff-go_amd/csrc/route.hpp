@@ -1,0 +1,49 @@
+// route.hpp — the routing stage behind the nffacl_router handle (internal).
+//
+// The reference does not hand verdicts back: segmentProcess appends every
+// packet of a burst to OutputMbufs[answer] in arrival order and enqueues one
+// slice per output flow (flow/flow.go:1462-1486; the vector form through
+// asm.GenerateMask, flow.go:1505-1517).  That is a stable partition of the
+// burst by answer.  Here the burst is a batch of up to 2^31 verdicts in HBM
+// and the partition is three ordinary launches (route.hip): per-tile counts,
+// one exclusive scan of them, a per-tile stable scatter.  No workgroup waits
+// on another one.
+//
+// A tile is kRouteTile = 1024 threads x 8 keys.  A packet's bucket is
+//   SEPARATE  port != 0                       (separate, flow.go:1795-1797)
+//   SPLIT     min(port, n_out)                (makeSplitter, flow.go:1161)
+// so there are n_out + 1 buckets, the last one holding the out-of-range
+// answers (empty in SEPARATE mode).  The scratch is the count matrix
+// counts[bucket * tiles + tile] (bucket-major: its exclusive scan in memory
+// order is every (bucket, tile)'s first position in d_index).
+#pragma once
+
+#include <hip/hip_runtime.h>
+
+#include <cstdint>
+
+#include "nffacl.h"
+
+namespace nffacl {
+
+constexpr uint32_t kRouteBlock = 1024;                      // threads per tile workgroup (16 waves)
+constexpr uint32_t kRouteRounds = 8;                        // keys per thread
+constexpr uint32_t kRouteTile = kRouteBlock * kRouteRounds; // 8192 keys
+constexpr uint64_t kRouteMaxN = uint64_t(1) << 31;
+constexpr uint32_t kRouteMaxOut = 255;
+
+// Key bits of the kernels' template parameter: the smallest of 1, 2, 4, 8
+// that holds a bucket number 0..n_out.
+inline int route_key_bits(uint32_t n_out) { return n_out < 2 ? 1 : n_out < 4 ? 2 : n_out < 16 ? 4 : 8; }
+
+}  // namespace nffacl
+
+struct nffacl_router {
+    int device = 0;
+    uint32_t mode = NFFACL_ROUTE_SEPARATE;
+    uint32_t n_out = 2;
+    uint64_t max_n = 0;
+    uint32_t *d_counts = nullptr;  // (n_out + 1) * tiles(max_n) dwords
+    hipEvent_t last = nullptr;     // recorded behind every launch; destroy waits on it
+    bool used = false;
+};

@@ -157,6 +157,11 @@ _group_size = _sig("nffacl_group_size", _i, _vp)
 _group_classify = _sig("nffacl_group_classify_device", _i, _vp, _vp, _u32, ctypes.c_uint64, _vp, _vp, _vp)
 _group_destroy = _sig("nffacl_group_destroy", None, _vp)
 _group_shard = _sig("nffacl_group_shard", _i, _u64, _i, _i, ctypes.POINTER(_u64), ctypes.POINTER(_u64))
+_router_create = _sig("nffacl_router_create", _i, _i, _u32, _u32, _u64, _pp)
+_route_device = _sig("nffacl_route_device", _i, _vp, _vp, _u64, _vp, _vp, _vp)
+_route_gather = _sig("nffacl_route_gather_device", _i, _vp, _u32, _vp, _u64, _vp, _vp)
+_route_plan = _sig("nffacl_route_plan", _i, _u64, _u32, ctypes.POINTER(_u64), ctypes.POINTER(_u64))
+_router_destroy = _sig("nffacl_router_destroy", None, _vp)
 
 
 class KernelInfo(ctypes.Structure):
@@ -204,6 +209,8 @@ EXPORTED_SYMBOLS = [
     "nffacl_service_destroy", "nffacl_service_create_burst", "nffacl_service_classify_burst",
     "nffacl_service_pause", "nffacl_pick_device", "nffacl_group_create", "nffacl_group_size",
     "nffacl_group_classify_device", "nffacl_group_destroy", "nffacl_group_shard", "nffacl_engine_kernel_info",
+    "nffacl_router_create", "nffacl_route_device", "nffacl_route_gather_device", "nffacl_route_plan",
+    "nffacl_router_destroy",
 ]
 
 
@@ -505,6 +512,68 @@ class Engine:
 
     def L3ACLPermit(self, slots: np.ndarray, stride: int):
         return self.classify_host(slots, stride)[1].astype(bool)
+
+
+ROUTE_SEPARATE, ROUTE_SPLIT = 0, 1
+
+
+def route_plan(n: int, n_out: int):
+    """nffacl_route_plan: (tiles, scratch bytes) of routing n packets to n_out outputs."""
+    tiles, scratch = _u64(), _u64()
+    st = _route_plan(n, n_out, ctypes.byref(tiles), ctypes.byref(scratch))
+    if st != OK:
+        _raise(st, "nffacl_route_plan")
+    return tiles.value, scratch.value
+
+
+class Router:
+    """nffacl_router: the per-output index lists of a classified batch, on the
+    device — what segmentProcess builds per burst (OutputMbufs[answer],
+    flow/flow.go:1462-1486).  ROUTE_SEPARATE: n_out = 2, output = port != 0
+    (SetSeparator); ROUTE_SPLIT: output = port, ports >= n_out in one extra
+    segment at the end (SetSplitter).  One router per stream."""
+
+    def __init__(self, mode: int, n_out: int, max_n: int, device: int = 0):
+        out = ctypes.c_void_p()
+        st = _router_create(device, mode, n_out, max_n, ctypes.byref(out))
+        if st != OK:
+            _raise(st, "nffacl_router_create")
+        self._h = out.value
+        self.device = device
+        self.n_out = n_out
+
+    def close(self):
+        h, self._h = getattr(self, "_h", None), None
+        if h and _router_destroy is not None:
+            try:
+                _router_destroy(h)
+            except Exception:  # interpreter teardown
+                pass
+
+    def __del__(self):
+        self.close()
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def route(self, port, n: int, index, offsets, stream=None):
+        """index[n] <- the stable partition of 0..n-1 by output, offsets[n_out + 2]
+        <- the segment bounds (uint32 device buffers).  Asynchronous on `stream`."""
+        s = stream.cuda_stream if hasattr(stream, "cuda_stream") else stream
+        st = _route_device(self._h, _ptr(port), n, _ptr(index), _ptr(offsets), s)
+        if st != OK:
+            _raise(st, "nffacl_route_device")
+
+    @staticmethod
+    def gather(slots, stride: int, index, m: int, out, stream=None):
+        """out slot j <- slot index[j] of slots, j < m (device buffers)."""
+        s = stream.cuda_stream if hasattr(stream, "cuda_stream") else stream
+        st = _route_gather(_ptr(slots), stride, _ptr(index), m, _ptr(out), s)
+        if st != OK:
+            _raise(st, "nffacl_route_gather_device")
 
 
 class Batcher:
