@@ -341,6 +341,65 @@ NFFACL_API int nffacl_classify_host(nffacl_engine *eng, const uint8_t *h_slots, 
 NFFACL_API int nffacl_classify_host_ex(nffacl_engine *eng, const uint8_t *h_slots, uint32_t stride,
                                        uint64_t n, uint32_t *h_port, uint8_t *h_permit, uint32_t flags);
 
+/* ---- compact 5-tuple keys (additive to ABI 7) -----------------------------
+ *
+ * The walk needs only what the header parse extracts: family, protocol, two
+ * ports, two addresses.  A key holds exactly those fields of one packet — 16
+ * bytes for IPv4 instead of a 64-byte slot — so a flow-function clone that
+ * fills keys moves a quarter of the bytes over PCIe / xGMI / HBM, and a batch
+ * parsed once can be classified against several rule sets or again after
+ * nffacl_engine_swap_rules without touching packet bytes.  Reference
+ * interfaces stood for:
+ *   nffacl_extract_keys_device / _host <- ParseAllKnownL3 (packet.go:353-363;
+ *       ParseAllKnownL3CheckVLAN, vlan.go:104-117, under NFFACL_PARSE_VLAN) +
+ *       ParseL4ForIPv4/6 (packet.go:278-285) and the field reads of l3ACL /
+ *       l4ACL (acl.go:508-565), done once per packet
+ *   nffacl_classify_keys_device <- (*Packet).L3ACLPort / L3ACLPermit
+ *       (acl.go:495-506) over the extracted fields of a batch in HBM
+ *   nffacl_classify_keys_host   <- the VectorSeparateFunction body
+ *       (flow/flow.go:131, 1487-1520), keys in, verdicts out
+ * A key is what the parse yields for its packet: ports come from wherever IHL
+ * puts them, bytes past the frame read as 0, ports are read for ICMP too, a
+ * VLAN tag is honoured only under NFFACL_PARSE_VLAN. */
+typedef struct nffacl_key {   /* 16 bytes; arrays 16-byte aligned */
+    uint32_t a;      /* family 4: src, a types.IPv4Address as in nffacl_rule4.src_addr
+                        family 6: index of this packet's nffacl_key6 record */
+    uint32_t b;      /* family 4: dst; family 6: 0 */
+    uint32_t ports;  /* sport | dport << 16, host-order numbers */
+    uint32_t meta;   /* bits 0-7 L4 protocol, bits 8-15 family (0 = neither, 4, 6), rest 0 */
+} nffacl_key;
+typedef struct nffacl_key6 { uint8_t src[16]; uint8_t dst[16]; } nffacl_key6; /* wire order, 32 bytes */
+
+/* d_port / d_permit_bits / stream as nffacl_classify_device, for n keys in
+ * HBM (d_keys and d_key6 16-byte aligned; d_key6 may be NULL when n_key6 is
+ * 0).  A key of family 0, of an unknown family, or of family 6 with an index
+ * >= n_key6 gets verdict 0, and nothing outside the two arrays is read.
+ * Serves every table an engine can hold.  The key kernels take static
+ * batches (no per-stream counters): launches may be captured and replayed
+ * freely. */
+NFFACL_API int nffacl_classify_keys_device(nffacl_engine *eng, const nffacl_key *d_keys,
+                                           const nffacl_key6 *d_key6, uint32_t n_key6, uint64_t n,
+                                           uint32_t *d_port, uint64_t *d_permit_bits, void *stream);
+/* d_keys[i] <- the key of slot i (slots as nffacl_classify_device, flags as
+ * nffacl_parse_flags); an IPv6 packet's record goes to d_key6[i] and its key
+ * carries index i, so d_key6 holds n records and only IPv6 packets write
+ * theirs (classify with n_key6 = n).  n < 2^32.  Asynchronous on `stream`. */
+NFFACL_API int nffacl_extract_keys_device(const uint8_t *d_slots, uint32_t stride, uint64_t n, uint32_t flags,
+                                          nffacl_key *d_keys, nffacl_key6 *d_key6, void *stream);
+/* The same on the CPU, for the clones: frames[i] points at packet i's Ether
+ * header, lens[i] is its readable bytes (bytes past it read as 0).  IPv6
+ * records are packed densely into key6[0, *n_key6) in arrival order;
+ * NFFACL_ERR_INVALID_ARG (nothing promised about the outputs) when more than
+ * key6_cap are needed.  key6 may be NULL when key6_cap is 0. */
+NFFACL_API int nffacl_extract_keys_host(const uint8_t *const *frames, const uint32_t *lens, uint64_t n,
+                                        uint32_t flags, nffacl_key *keys, nffacl_key6 *key6, uint64_t key6_cap,
+                                        uint64_t *n_key6);
+/* Host keys in, host verdicts out (outputs as nffacl_classify_host), through
+ * the engine's chunked pinned staging: pinned 16-byte aligned key arrays are
+ * read by the kernel where they lie, pageable ones are staged.  Synchronous. */
+NFFACL_API int nffacl_classify_keys_host(nffacl_engine *eng, const nffacl_key *h_keys, const nffacl_key6 *h_key6,
+                                         uint32_t n_key6, uint64_t n, uint32_t *h_port, uint8_t *h_permit);
+
 /* ---- burst aggregator (host ingest) ----------------
  *
  * Many threads (the reference's flow-function clones, each with a burst of

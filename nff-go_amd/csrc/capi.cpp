@@ -13,6 +13,7 @@
 
 #include "devutil.hpp"
 #include "engine.hpp"
+#include "keys.hpp"
 #include "l2.hpp"
 #include "nffacl.h"
 #include "compile.hpp"
@@ -531,6 +532,90 @@ int nffacl_classify_host_ex(nffacl_engine *eng, const uint8_t *h_slots, uint32_t
             in = eng->d_slots[b];
         }
         st = launch_slots(eng, t.get(), in, stride, cnt, out, nullptr, eng->streams[b], flags);
+        if (st != NFFACL_OK) return st;
+        HIP_CHECK(hipEventRecord(eng->done[b], eng->streams[b]));
+        pending_chunk[b] = c;
+    }
+    for (uint64_t c = nchunks > uint64_t(nb) ? nchunks - nb : 0; c < nchunks; ++c)  // completion order
+        if ((st = drain(static_cast<int>(c % uint64_t(nb)))) != NFFACL_OK) return st;
+    return NFFACL_OK;
+}
+
+// Keys in host memory (keys.hip): the chunked scheme of nffacl_classify_host_ex
+// over its staging.  Pinned, 16-byte aligned key arrays are read by the
+// kernel where they lie (16 B per IPv4 packet over the link instead of 64).
+// Otherwise a chunk's keys are copied into the chunk's pinned stage with the
+// IPv6 records they name packed behind them (indices rewritten chunk-local,
+// out-of-range ones to 0xFFFFFFFF: verdict 0) — at most 48 bytes per key in a
+// stage that holds 64 — and DMA'd to the chunk's HBM buffer.
+int nffacl_classify_keys_host(nffacl_engine *eng, const nffacl_key *h_keys, const nffacl_key6 *h_key6,
+                              uint32_t n_key6, uint64_t n, uint32_t *h_port, uint8_t *h_permit) {
+    if (!eng || (!h_port && !h_permit)) return NFFACL_ERR_INVALID_ARG;
+    if (n == 0) return NFFACL_OK;
+    if (!h_keys || reinterpret_cast<uintptr_t>(h_keys) % 16 != 0 || (n_key6 && !h_key6) ||
+        reinterpret_cast<uintptr_t>(h_key6) % 16 != 0)
+        return NFFACL_ERR_INVALID_ARG;
+    std::lock_guard<std::mutex> g(eng->host_mu);
+    HIP_CHECK(hipSetDevice(eng->device));
+    int st = ensure_host_pipeline(eng, 64, n);
+    if (st != NFFACL_OK) return st;
+    const TablePtr t = acquire_table(eng);  // one table for every chunk of this call
+    const nffacl_key *d_host_keys =
+        range_is_pinned(h_keys, n * sizeof(nffacl_key)) ? static_cast<const nffacl_key *>(host_alias(h_keys)) : nullptr;
+    const nffacl_key6 *d_host_key6 = n_key6 && range_is_pinned(h_key6, size_t(n_key6) * sizeof(nffacl_key6))
+                                         ? static_cast<const nffacl_key6 *>(host_alias(h_key6))
+                                         : nullptr;
+    const bool zero_copy = d_host_keys && (n_key6 == 0 || d_host_key6) && eng->tune.host_dma == 0;
+    uint32_t *d_host_port = nullptr;
+    if (h_port && range_is_pinned(h_port, n * 4) && reinterpret_cast<uintptr_t>(h_port) % 4 == 0)
+        d_host_port = static_cast<uint32_t *>(host_alias(h_port));
+    const uint64_t chunk = eng->chunk;
+    const int nb = eng->nbufs;
+    const uint64_t nchunks = (n + chunk - 1) / chunk;
+    uint64_t pending_chunk[nffacl_engine::kHostBufs];
+    for (int b = 0; b < nffacl_engine::kHostBufs; ++b) pending_chunk[b] = ~0ull;
+    auto drain = [&](int b) -> int {
+        if (pending_chunk[b] == ~0ull) return NFFACL_OK;
+        HIP_CHECK(hipEventSynchronize(eng->done[b]));
+        const uint64_t first = pending_chunk[b] * chunk;
+        const uint64_t cnt = std::min<uint64_t>(chunk, n - first);
+        const uint32_t *res = d_host_port ? h_port + first : eng->h_port[b];
+        if (h_port && !d_host_port) std::memcpy(h_port + first, res, cnt * 4);
+        if (h_permit)
+            for (uint64_t i = 0; i < cnt; ++i) h_permit[first + i] = res[i] != 0;
+        pending_chunk[b] = ~0ull;
+        return NFFACL_OK;
+    };
+    for (uint64_t c = 0; c < nchunks; ++c) {
+        const int b = static_cast<int>(c % uint64_t(nb));
+        if ((st = drain(b)) != NFFACL_OK) return st;
+        const uint64_t first = c * chunk;
+        const uint64_t cnt = std::min<uint64_t>(chunk, n - first);
+        uint32_t *out = d_host_port ? d_host_port + first : eng->d_hport[b];
+        if (zero_copy) {
+            st = launch_keys(eng, t.get(), d_host_keys + first, d_host_key6, n_key6, cnt, out, nullptr, eng->streams[b]);
+        } else {
+            nffacl_key *sk = reinterpret_cast<nffacl_key *>(eng->h_stage[b]);
+            nffacl_key6 *s6 = reinterpret_cast<nffacl_key6 *>(eng->h_stage[b] + cnt * sizeof(nffacl_key));
+            uint32_t m6 = 0;
+            for (uint64_t i = 0; i < cnt; ++i) {
+                nffacl_key k = h_keys[first + i];
+                if ((k.meta >> 8) == 6u) {
+                    if (k.a < n_key6) {
+                        s6[m6] = h_key6[k.a];
+                        k.a = m6++;
+                    } else {
+                        k.a = 0xFFFFFFFFu;
+                    }
+                }
+                sk[i] = k;
+            }
+            const size_t bytes = cnt * sizeof(nffacl_key) + size_t(m6) * sizeof(nffacl_key6);
+            HIP_CHECK(hipMemcpyAsync(eng->d_slots[b], eng->h_stage[b], bytes, hipMemcpyHostToDevice, eng->streams[b]));
+            st = launch_keys(eng, t.get(), reinterpret_cast<const nffacl_key *>(eng->d_slots[b]),
+                             reinterpret_cast<const nffacl_key6 *>(eng->d_slots[b] + cnt * sizeof(nffacl_key)), m6, cnt,
+                             out, nullptr, eng->streams[b]);
+        }
         if (st != NFFACL_OK) return st;
         HIP_CHECK(hipEventRecord(eng->done[b], eng->streams[b]));
         pending_chunk[b] = c;

@@ -31,6 +31,7 @@
 #include "compile.hpp"
 #include "devutil.hpp"
 #include "engine.hpp"
+#include "launch.hpp"
 #include "service.hpp"
 
 namespace nffacl {
@@ -585,7 +586,7 @@ int upload_table(nffacl_engine *eng, const nffacl_rules &rules, TablePtr &out) {
     return NFFACL_OK;
 }
 
-static uint32_t grid_for(const nffacl_engine *eng, uint64_t n, uint32_t block, uint32_t per_cu) {
+uint32_t grid_for(const nffacl_engine *eng, uint64_t n, uint32_t block, uint32_t per_cu) {
     const uint64_t waves_needed = (n + 63) / 64;
     const uint64_t blocks_needed = (waves_needed * 64 + block - 1) / block;
     const uint64_t cap = uint64_t(eng->num_cus) * per_cu;
@@ -603,7 +604,7 @@ static uint32_t field_of(uint32_t kind) {
     }
 }
 
-static dev::IndexedArgs indexed_args(const DevTable *t) {
+dev::IndexedArgs indexed_args(const DevTable *t) {
     dev::IndexedArgs a{};
     a.tab = t->d_blob;
     const bool hyb = t->meta.algo == NFFACL_ALGO_HYBRID;
@@ -638,20 +639,12 @@ static dev::IndexedArgs indexed_args(const DevTable *t) {
     return a;
 }
 
-// LDS budget per workgroup for a staged table (gfx950: 160 KiB per CU).
-constexpr size_t kLdsBytes = 160 * 1024;
-
-struct IndexedLaunch {
-    int tm;  // dev::TableMode
-    int ns;
-    uint32_t block, per_cu;
-    size_t lds_bytes;
-};
+// (kLdsBytes, IndexedLaunch: launch.hpp)
 
 // The kernel a table gets must match the layout it was compiled to: checked
 // on the host before every indexed launch (a mismatch would read the blob
 // with the wrong offsets).
-static bool table_consistent(const DevTable *t) {
+bool table_consistent(const DevTable *t) {
     const CompiledTable &m = t->meta;
     const size_t dw = m.blob.size();
     // entry numbers (and list offsets) stay below 2^23: the kernels scale
@@ -681,7 +674,7 @@ static bool table_consistent(const DevTable *t) {
 #endif
 
 // Launch shape of an indexed table; Tune overrides (frozen at engine creation).
-static IndexedLaunch indexed_launch(const nffacl_engine *eng, const DevTable *t) {
+IndexedLaunch indexed_launch(const nffacl_engine *eng, const DevTable *t) {
     const Tune &tu = eng->tune;
     const uint32_t used = std::max(t->meta.idx4.used_slots, t->meta.idx6.used_slots);
     const int ns = used <= 2 ? 2 : static_cast<int>(used);

@@ -162,6 +162,15 @@ _route_device = _sig("nffacl_route_device", _i, _vp, _vp, _u64, _vp, _vp, _vp)
 _route_gather = _sig("nffacl_route_gather_device", _i, _vp, _u32, _vp, _u64, _vp, _vp)
 _route_plan = _sig("nffacl_route_plan", _i, _u64, _u32, ctypes.POINTER(_u64), ctypes.POINTER(_u64))
 _router_destroy = _sig("nffacl_router_destroy", None, _vp)
+_classify_keys_device = _sig("nffacl_classify_keys_device", _i, _vp, _vp, _vp, _u32, _u64, _vp, _vp, _vp)
+_extract_keys_device = _sig("nffacl_extract_keys_device", _i, _vp, _u32, _u64, _u32, _vp, _vp, _vp)
+_extract_keys_host = _sig("nffacl_extract_keys_host", _i, _vp, _vp, _u64, _u32, _vp, _vp, _u64, ctypes.POINTER(_u64))
+_classify_keys_host = _sig("nffacl_classify_keys_host", _i, _vp, _vp, _vp, _u32, _u64, _vp, _vp)
+
+# nffacl_key / nffacl_key6 (include/nffacl.h): the fields of one packet
+KEY_DTYPE = np.dtype([("a", "<u4"), ("b", "<u4"), ("ports", "<u4"), ("meta", "<u4")])
+KEY6_DTYPE = np.dtype([("src", "u1", 16), ("dst", "u1", 16)])
+assert KEY_DTYPE.itemsize == 16 and KEY6_DTYPE.itemsize == 32
 
 
 class KernelInfo(ctypes.Structure):
@@ -210,7 +219,8 @@ EXPORTED_SYMBOLS = [
     "nffacl_service_pause", "nffacl_pick_device", "nffacl_group_create", "nffacl_group_size",
     "nffacl_group_classify_device", "nffacl_group_destroy", "nffacl_group_shard", "nffacl_engine_kernel_info",
     "nffacl_router_create", "nffacl_route_device", "nffacl_route_gather_device", "nffacl_route_plan",
-    "nffacl_router_destroy",
+    "nffacl_router_destroy", "nffacl_classify_keys_device", "nffacl_extract_keys_device",
+    "nffacl_extract_keys_host", "nffacl_classify_keys_host",
 ]
 
 
@@ -506,12 +516,63 @@ class Engine:
             _raise(st, "nffacl_classify_host")
         return port, perm
 
+    def classify_keys_device(self, keys, key6, n_key6: int, n: int, port=None, permit_bits=None, stream=None):
+        """nffacl_classify_keys_device: n nffacl_key records (and the
+        nffacl_key6 records they index; None when n_key6 is 0) in device
+        memory.  Asynchronous on `stream`."""
+        s = stream.cuda_stream if hasattr(stream, "cuda_stream") else stream
+        st = _classify_keys_device(self._h, _ptr(keys), _ptr(key6), n_key6, n, _ptr(port), _ptr(permit_bits), s)
+        if st != OK:
+            _raise(st, "nffacl_classify_keys_device")
+
+    def classify_keys_host(self, keys: np.ndarray, key6: np.ndarray | None = None, n: int | None = None,
+                           out: np.ndarray | None = None, permit: bool = True):
+        """Host keys (KEY_DTYPE[n], KEY6_DTYPE[...]) -> (port uint32[n], permit
+        uint8[n] or None); `out` / `permit` as classify_host."""
+        if n is None:
+            n = len(keys)
+        n6 = 0 if key6 is None else len(key6)
+        port = np.zeros(n, np.uint32) if out is None else out
+        if port.dtype != np.uint32 or port.size < n or not port.flags.c_contiguous:
+            raise ValueError("out: contiguous uint32[n] expected")
+        perm = np.zeros(n, np.uint8) if permit else None
+        st = _classify_keys_host(self._h, _ptr(keys), _ptr(key6) if n6 else None, n6, n, port.ctypes.data,
+                                 perm.ctypes.data if permit else None)
+        if st != OK:
+            _raise(st, "nffacl_classify_keys_host")
+        return port, perm
+
     # Batch forms of the reference's per-packet API (acl.go:495-506)
     def L3ACLPort(self, slots: np.ndarray, stride: int):
         return self.classify_host(slots, stride)[0]
 
     def L3ACLPermit(self, slots: np.ndarray, stride: int):
         return self.classify_host(slots, stride)[1].astype(bool)
+
+
+def extract_keys_device(slots, stride: int, n: int, keys, key6, flags: int = 0, stream=None):
+    """nffacl_extract_keys_device: keys[i] <- the key of device slot i, an IPv6
+    packet's record to key6[i] (both device buffers of n records)."""
+    s = stream.cuda_stream if hasattr(stream, "cuda_stream") else stream
+    st = _extract_keys_device(_ptr(slots), stride, n, flags, _ptr(keys), _ptr(key6), s)
+    if st != OK:
+        _raise(st, "nffacl_extract_keys_device")
+
+
+def extract_keys_host(ptrs: np.ndarray, lens: np.ndarray, flags: int = 0, key6_cap: int | None = None):
+    """nffacl_extract_keys_host: frame addresses (uint64[n], Batcher.frame_pointers)
+    and lengths (uint32[n]) -> (keys KEY_DTYPE[n], key6 KEY6_DTYPE[n_key6]),
+    IPv6 records dense in arrival order; key6_cap defaults to n."""
+    ptrs = np.ascontiguousarray(ptrs, np.uint64)
+    lens = np.ascontiguousarray(lens, np.uint32)
+    n = len(ptrs)
+    cap = n if key6_cap is None else key6_cap
+    keys, key6, n6 = np.zeros(n, KEY_DTYPE), np.zeros(cap, KEY6_DTYPE), _u64()
+    st = _extract_keys_host(ptrs.ctypes.data, lens.ctypes.data, n, flags, keys.ctypes.data,
+                            key6.ctypes.data if cap else None, cap, ctypes.byref(n6))
+    if st != OK:
+        _raise(st, "nffacl_extract_keys_host")
+    return keys, key6[:n6.value]
 
 
 ROUTE_SEPARATE, ROUTE_SPLIT = 0, 1
