@@ -21,6 +21,10 @@
  *                                  ParseL4ForIPv4/6 packet.go:278-285 — over a batch of
  *                                  packets resident in HBM
  *   nffacl_classify_frames_device  same, over packed variable-length frames (IMIX)
+ *   nffacl_extract_keys_frames_device  the same parse over packed frames, into 16-byte keys
+ *   nffacl_route_gather_frames_device <- the per-output packet slices of segmentProcess
+ *                                  (flow/flow.go:1462-1486) as packed frames with
+ *                                  descriptors, gathered through a route's index lists
  *   nffacl_classify_host        <- the VectorSeparateFunction body the reference runs per
  *                                  burst (flow/flow.go:131, 1487-1520;
  *                                  test/stability/testSingleWorkingFF/testSingleWorkingFF.go:538-546)
@@ -386,6 +390,13 @@ NFFACL_API int nffacl_classify_keys_device(nffacl_engine *eng, const nffacl_key 
  * theirs (classify with n_key6 = n).  n < 2^32.  Asynchronous on `stream`. */
 NFFACL_API int nffacl_extract_keys_device(const uint8_t *d_slots, uint32_t stride, uint64_t n, uint32_t flags,
                                           nffacl_key *d_keys, nffacl_key6 *d_key6, void *stream);
+/* d_keys[i] <- the key of frame i (frames as nffacl_classify_frames_device, flags as
+ * nffacl_parse_flags): the parse of ParseAllKnownL3 (packet.go:353-363) over
+ * packed frames, bytes past a frame's length read as 0.  key6 placement and
+ * limits as nffacl_extract_keys_device. */
+NFFACL_API int nffacl_extract_keys_frames_device(const uint8_t *d_frames, const uint64_t *d_desc, uint64_t n,
+                                                 uint32_t flags, nffacl_key *d_keys, nffacl_key6 *d_key6,
+                                                 void *stream);
 /* The same on the CPU, for the clones: frames[i] points at packet i's Ether
  * header, lens[i] is its readable bytes (bytes past it read as 0).  IPv6
  * records are packed densely into key6[0, *n_key6) in arrival order;
@@ -694,6 +705,40 @@ NFFACL_API int nffacl_route_gather_device(const uint8_t *d_slots, uint32_t strid
  * the scratch bytes a router of max_n = n holds, tiles * (n_out + 1) * 4.
  * NFFACL_ERR_INVALID_ARG for n > 2^31, n_out outside 1..255 or NULL outputs. */
 NFFACL_API int nffacl_route_plan(uint64_t n, uint32_t n_out, uint64_t *tiles, uint64_t *scratch_bytes);
+/* The per-output packet lists of segmentProcess (flow/flow.go:1462-1486) for
+ * packed frames.  Output frame j (j < m) <- frame d_index[j] of (d_frames,
+ * d_desc[0..n)), packed:
+ *   room(len)     = len rounded up to `align` (a power of two, 16..4096)
+ *   off_j         = sum_{k<j} room(len_k)                       (64-bit)
+ *   d_out_desc[j] = off_j << 16 | len_j
+ *   d_out[off_j, off_j+len_j) = the frame's bytes; [off_j+len_j, off_j+room) = 0
+ *   *d_out_bytes  = sum of all rooms (the bytes the packed batch needs)
+ * so (d_out, d_out_desc) is a frames batch for nffacl_classify_frames_device.
+ * Called with the whole d_index of a route it yields every output's frames
+ * back to back (d_offsets cuts d_out_desc into the outputs); with d_index +
+ * offsets[o] and that output's count, one output.
+ * d_index[j] >= n counts as an empty frame (len 0; nothing is read for it).
+ * Nothing at or past d_out + out_cap is written (out_cap % 16 == 0).  16-byte
+ * chunks wholly below it are written, and d_out_desc and *d_out_bytes are
+ * complete either way, so the caller sees from *d_out_bytes > out_cap that the
+ * buffer was short.
+ * Source frames as nffacl_classify_frames_device: 16-byte aligned starts
+ * (d_frames and d_out 16-byte aligned).  A 16-byte chunk is read only if it
+ * starts inside its frame.  Bytes past len in the last chunk are not copied
+ * (zeroed).  d_index may repeat an index.
+ * m <= the router's max_n.  m = 0 writes only *d_out_bytes = 0.  Asynchronous
+ * on `stream` (three kernel launches); launches allocate nothing; recorded on
+ * the router's event like nffacl_route_device, and sharing its one-stream
+ * rule.  NFFACL_ERR_INVALID_ARG for a bad align or out_cap, NULL or misaligned
+ * buffers, m > max_n. */
+NFFACL_API int nffacl_route_gather_frames_device(nffacl_router *r, const uint8_t *d_frames, const uint64_t *d_desc,
+                                                 uint64_t n, const uint32_t *d_index, uint64_t m, uint32_t align,
+                                                 uint8_t *d_out, uint64_t out_cap, uint64_t *d_out_desc,
+                                                 uint64_t *d_out_bytes, void *stream);
+/* Its plan (pure, no device): tiles = ceil(m / frames-per-tile);
+ * scratch_bytes = what a router of max_n = m holds for this path (one 64-bit
+ * sum per tile).  NFFACL_ERR_INVALID_ARG for m > 2^31 or NULL outputs. */
+NFFACL_API int nffacl_route_frames_plan(uint64_t m, uint64_t *tiles, uint64_t *scratch_bytes);
 /* Waits for the router's last launch (its own event, no device-wide
  * synchronise), then frees. */
 NFFACL_API void nffacl_router_destroy(nffacl_router *r);

@@ -185,10 +185,23 @@ k_keys(const u32x4 *__restrict__ keys, const u32x4 *__restrict__ key6, uint32_t 
                                                     [&](const Fields &f) { return walk_key<NS, TM>(a, f, lane); });
 }
 
+// Packet idx's key from its parsed fields: each lane writes its own 16-byte
+// key (lane-contiguous dwordx4 stores), IPv6 lanes their 32-byte record at
+// their packet's index.
+__device__ __forceinline__ void store_key(const Fields &f, uint64_t idx, bool live, u32x4 *__restrict__ keys,
+                                          u32x4 *__restrict__ key6) {
+    u32x4 k = {0u, 0u, 0u, 0u};  // neither family: the zero key
+    if (f.is4) k = u32x4{f.s[0], f.t[0], f.ports, (f.proto & 0xFFu) | kFam4 << 8};
+    if (f.is6) k = u32x4{static_cast<uint32_t>(idx), 0u, f.ports, (f.proto & 0xFFu) | kFam6 << 8};
+    if (live) keys[idx] = k;
+    if (f.is6) {  // (is6 implies live)
+        key6[2 * idx] = u32x4{f.s[0], f.s[1], f.s[2], f.s[3]};
+        key6[2 * idx + 1] = u32x4{f.t[0], f.t[1], f.t[2], f.t[3]};
+    }
+}
+
 // Slots -> keys.  Dense 64-byte slots load lane-contiguous (devutil.hpp
 // load_rowswap: lane l ends with packet l); wider strides one row per lane.
-// Each lane writes its own 16-byte key (lane-contiguous dwordx4 stores), IPv6
-// lanes their 32-byte record at their packet's index.
 __global__ void __launch_bounds__(256)
 k_extract_keys(const uint8_t *__restrict__ slots, uint32_t stride, uint64_t n, uint32_t flags,
                u32x4 *__restrict__ keys, u32x4 *__restrict__ key6) {
@@ -208,14 +221,38 @@ k_extract_keys(const uint8_t *__restrict__ slots, uint32_t stride, uint64_t n, u
         parse_fields(d, live, f, [&](uint32_t k, uint32_t &lo, uint32_t &hi) {
             far_dwords(pkt, stride, k, lo, hi);
         }, flags);
-        u32x4 k = {0u, 0u, 0u, 0u};  // neither family: the zero key
-        if (f.is4) k = u32x4{f.s[0], f.t[0], f.ports, (f.proto & 0xFFu) | kFam4 << 8};
-        if (f.is6) k = u32x4{static_cast<uint32_t>(idx), 0u, f.ports, (f.proto & 0xFFu) | kFam6 << 8};
-        if (live) keys[idx] = k;
-        if (f.is6) {  // (is6 implies live)
-            key6[2 * idx] = u32x4{f.s[0], f.s[1], f.s[2], f.s[3]};
-            key6[2 * idx + 1] = u32x4{f.t[0], f.t[1], f.t[2], f.t[3]};
+        store_key(f, idx, live, keys, key6);
+    }
+}
+
+// Packed frames -> keys (desc = offset << 16 | len, as k_linear_frames).  A
+// full wave loads its 64 descriptors lane-contiguous and its frame lines
+// cooperatively (load_frames_rs: whole 64-byte lines per instruction); the
+// ragged last wave reads one frame per lane.  Ports past byte 63 (IHL >= 12,
+// VLAN) come through the frames far reader: bytes past len read as 0.
+__global__ void __launch_bounds__(256)
+k_extract_keys_frames(const uint8_t *__restrict__ frames, const uint64_t *__restrict__ desc, uint64_t n,
+                      uint32_t flags, u32x4 *__restrict__ keys, u32x4 *__restrict__ key6) {
+    NFFACL_WAVE_LOOP(n) {
+        const uint64_t idx = base + lane;
+        const bool live = idx < n;
+        const uint64_t ds = live ? desc[idx] : 0;
+        const uint32_t len = static_cast<uint32_t>(ds & 0xFFFFu);
+        const uint8_t *pkt = frames + (ds >> 16);
+        uint32_t d[16];
+        if (base + 64 <= n) {
+            u32x4 v[4];
+            load_frames_rs(frames, ds, lane, v);
+            rowswap_batch(v, d);
+            if (ballot(len < 64u)) clip16(d, len);
+        } else {
+            load16_frame(pkt, len, d);
         }
+        Fields f;
+        parse_fields(d, live, f, [&](uint32_t k, uint32_t &lo, uint32_t &hi) {
+            far_dwords(pkt, len, k, lo, hi);
+        }, flags);
+        store_key(f, idx, live, keys, key6);
     }
 }
 
@@ -376,6 +413,22 @@ int nffacl_extract_keys_device(const uint8_t *d_slots, uint32_t stride, uint64_t
     const uint32_t grid = static_cast<uint32_t>(std::min<uint64_t>(blocks, 2048));
     hipLaunchKernelGGL(dev::k_extract_keys, dim3(grid), dim3(256), 0, static_cast<hipStream_t>(stream), d_slots,
                        stride, n, flags, reinterpret_cast<dev::u32x4 *>(d_keys),
+                       reinterpret_cast<dev::u32x4 *>(d_key6));
+    HIP_TRY(hipGetLastError());
+    return NFFACL_OK;
+}
+
+int nffacl_extract_keys_frames_device(const uint8_t *d_frames, const uint64_t *d_desc, uint64_t n, uint32_t flags,
+                                      nffacl_key *d_keys, nffacl_key6 *d_key6, void *stream) {
+    if ((flags & ~uint32_t(NFFACL_PARSE_VLAN)) != 0 || n >> 32) return NFFACL_ERR_INVALID_ARG;
+    if (n == 0) return NFFACL_OK;
+    if (!d_frames || !aligned16(d_frames) || !d_desc || !d_keys || !aligned16(d_keys) || !d_key6 ||
+        !aligned16(d_key6))
+        return NFFACL_ERR_INVALID_ARG;
+    const uint64_t blocks = (n + 255) / 256;  // (launch shape: as nffacl_extract_keys_device)
+    const uint32_t grid = static_cast<uint32_t>(std::min<uint64_t>(blocks, 2048));
+    hipLaunchKernelGGL(dev::k_extract_keys_frames, dim3(grid), dim3(256), 0, static_cast<hipStream_t>(stream),
+                       d_frames, d_desc, n, flags, reinterpret_cast<dev::u32x4 *>(d_keys),
                        reinterpret_cast<dev::u32x4 *>(d_key6));
     HIP_TRY(hipGetLastError());
     return NFFACL_OK;

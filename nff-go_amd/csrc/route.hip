@@ -37,23 +37,6 @@ __device__ __forceinline__ uint32_t rank_below(uint64_t m) {  // set bits of m b
     return __builtin_amdgcn_mbcnt_hi(static_cast<uint32_t>(m >> 32), __builtin_amdgcn_mbcnt_lo(static_cast<uint32_t>(m), 0u));
 }
 
-// Inclusive wave sum: row_shr 1, 2, 4, 8 inside the four 16-lane rows, then
-// lane 15 of rows 0 / 2 into rows 1 / 3 (row_bcast:15) and lane 31 into the
-// upper half (row_bcast:31).  A lane without a source adds `old` = 0.
-template <int CTRL, int ROWS>
-__device__ __forceinline__ uint32_t dpp_add(uint32_t x) {
-    return x + static_cast<uint32_t>(__builtin_amdgcn_update_dpp(0, static_cast<int>(x), CTRL, ROWS, 0xf, false));
-}
-__device__ __forceinline__ uint32_t wave_scan_incl(uint32_t x) {
-    x = dpp_add<0x111, 0xf>(x);
-    x = dpp_add<0x112, 0xf>(x);
-    x = dpp_add<0x114, 0xf>(x);
-    x = dpp_add<0x118, 0xf>(x);
-    x = dpp_add<0x142, 0xa>(x);
-    x = dpp_add<0x143, 0xc>(x);
-    return x;
-}
-
 // The wave's buckets of its 8 rounds of tile `tile`; bit r of `live` says
 // round r's packet exists (index < n).  Dead rounds get bucket 0 and take no
 // part in any count.
@@ -326,8 +309,9 @@ int nffacl_router_create(int hip_device, uint32_t mode, uint32_t n_out, uint64_t
     *out = nullptr;
     if (mode != NFFACL_ROUTE_SEPARATE && mode != NFFACL_ROUTE_SPLIT) return NFFACL_ERR_INVALID_ARG;
     if (mode == NFFACL_ROUTE_SEPARATE && n_out != 2) return NFFACL_ERR_INVALID_ARG;
-    uint64_t tiles = 0, bytes = 0;
+    uint64_t tiles = 0, bytes = 0, ftiles = 0, fbytes = 0;
     if (nffacl_route_plan(max_n, n_out, &tiles, &bytes) != NFFACL_OK) return NFFACL_ERR_INVALID_ARG;
+    if (nffacl_route_frames_plan(max_n, &ftiles, &fbytes) != NFFACL_OK) return NFFACL_ERR_INVALID_ARG;
     int count = 0;
     if (hipGetDeviceCount(&count) != hipSuccess || count <= 0) {
         (void)hipGetLastError();
@@ -343,6 +327,8 @@ int nffacl_router_create(int hip_device, uint32_t mode, uint32_t n_out, uint64_t
     r->n_out = n_out;
     r->max_n = max_n;
     hipError_t e = hipMalloc(reinterpret_cast<void **>(&r->d_counts), std::max<uint64_t>(bytes, sizeof(uint32_t)));
+    if (e == hipSuccess)
+        e = hipMalloc(reinterpret_cast<void **>(&r->d_fsums), std::max<uint64_t>(fbytes, sizeof(uint64_t)));
     if (e == hipSuccess) e = hipEventCreateWithFlags(&r->last, hipEventDisableTiming);
     if (e != hipSuccess) {
         set_last_error(std::string("router scratch: ") + hipGetErrorString(e));
@@ -399,6 +385,7 @@ void nffacl_router_destroy(nffacl_router *r) {
         (void)hipEventDestroy(r->last);
     }
     if (r->d_counts) (void)hipFree(r->d_counts);
+    if (r->d_fsums) (void)hipFree(r->d_fsums);
     (void)hipGetLastError();
     delete r;
 }

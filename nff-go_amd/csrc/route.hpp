@@ -36,6 +36,33 @@ constexpr uint32_t kRouteMaxOut = 255;
 // that holds a bucket number 0..n_out.
 inline int route_key_bits(uint32_t n_out) { return n_out < 2 ? 1 : n_out < 4 ? 2 : n_out < 16 ? 4 : 8; }
 
+// Packed-frame gather (route_frames.hip): a tile is kGatherfTile output
+// positions, one per thread of a kRouteBlock workgroup; the scratch is one
+// 64-bit sum per tile, the tile's rooms in 16-byte chunks (after the scan:
+// the tile's first output chunk).
+constexpr uint32_t kGatherfTile = kRouteBlock;
+
+namespace dev {
+
+// Inclusive wave sum: row_shr 1, 2, 4, 8 inside the four 16-lane rows, then
+// lane 15 of rows 0 / 2 into rows 1 / 3 (row_bcast:15) and lane 31 into the
+// upper half (row_bcast:31).  A lane without a source adds `old` = 0.
+template <int CTRL, int ROWS>
+__device__ __forceinline__ uint32_t dpp_add(uint32_t x) {
+    return x + static_cast<uint32_t>(__builtin_amdgcn_update_dpp(0, static_cast<int>(x), CTRL, ROWS, 0xf, false));
+}
+__device__ __forceinline__ uint32_t wave_scan_incl(uint32_t x) {
+    x = dpp_add<0x111, 0xf>(x);
+    x = dpp_add<0x112, 0xf>(x);
+    x = dpp_add<0x114, 0xf>(x);
+    x = dpp_add<0x118, 0xf>(x);
+    x = dpp_add<0x142, 0xa>(x);
+    x = dpp_add<0x143, 0xc>(x);
+    return x;
+}
+
+}  // namespace dev
+
 }  // namespace nffacl
 
 struct nffacl_router {
@@ -44,6 +71,7 @@ struct nffacl_router {
     uint32_t n_out = 2;
     uint64_t max_n = 0;
     uint32_t *d_counts = nullptr;  // (n_out + 1) * tiles(max_n) dwords
+    uint64_t *d_fsums = nullptr;   // nffacl_route_frames_plan(max_n): one sum per gather tile
     hipEvent_t last = nullptr;     // recorded behind every launch; destroy waits on it
     bool used = false;
 };

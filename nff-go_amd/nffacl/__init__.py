@@ -162,8 +162,12 @@ _route_device = _sig("nffacl_route_device", _i, _vp, _vp, _u64, _vp, _vp, _vp)
 _route_gather = _sig("nffacl_route_gather_device", _i, _vp, _u32, _vp, _u64, _vp, _vp)
 _route_plan = _sig("nffacl_route_plan", _i, _u64, _u32, ctypes.POINTER(_u64), ctypes.POINTER(_u64))
 _router_destroy = _sig("nffacl_router_destroy", None, _vp)
+_route_frames_plan = _sig("nffacl_route_frames_plan", _i, _u64, ctypes.POINTER(_u64), ctypes.POINTER(_u64))
+_route_gather_frames = _sig("nffacl_route_gather_frames_device", _i, _vp, _vp, _vp, _u64, _vp, _u64, _u32, _vp, _u64,
+                            _vp, _vp, _vp)
 _classify_keys_device = _sig("nffacl_classify_keys_device", _i, _vp, _vp, _vp, _u32, _u64, _vp, _vp, _vp)
 _extract_keys_device = _sig("nffacl_extract_keys_device", _i, _vp, _u32, _u64, _u32, _vp, _vp, _vp)
+_extract_keys_frames = _sig("nffacl_extract_keys_frames_device", _i, _vp, _vp, _u64, _u32, _vp, _vp, _vp)
 _extract_keys_host = _sig("nffacl_extract_keys_host", _i, _vp, _vp, _u64, _u32, _vp, _vp, _u64, ctypes.POINTER(_u64))
 _classify_keys_host = _sig("nffacl_classify_keys_host", _i, _vp, _vp, _vp, _u32, _u64, _vp, _vp)
 
@@ -220,7 +224,8 @@ EXPORTED_SYMBOLS = [
     "nffacl_group_classify_device", "nffacl_group_destroy", "nffacl_group_shard", "nffacl_engine_kernel_info",
     "nffacl_router_create", "nffacl_route_device", "nffacl_route_gather_device", "nffacl_route_plan",
     "nffacl_router_destroy", "nffacl_classify_keys_device", "nffacl_extract_keys_device",
-    "nffacl_extract_keys_host", "nffacl_classify_keys_host",
+    "nffacl_extract_keys_host", "nffacl_classify_keys_host", "nffacl_route_frames_plan",
+    "nffacl_route_gather_frames_device", "nffacl_extract_keys_frames_device",
 ]
 
 
@@ -559,6 +564,15 @@ def extract_keys_device(slots, stride: int, n: int, keys, key6, flags: int = 0, 
         _raise(st, "nffacl_extract_keys_device")
 
 
+def extract_keys_frames_device(frames, desc, n: int, keys, key6, flags: int = 0, stream=None):
+    """nffacl_extract_keys_frames_device: keys[i] <- the key of packed frame i
+    (frames / desc as classify_frames_device), an IPv6 frame's record to key6[i]."""
+    s = stream.cuda_stream if hasattr(stream, "cuda_stream") else stream
+    st = _extract_keys_frames(_ptr(frames), _ptr(desc), n, flags, _ptr(keys), _ptr(key6), s)
+    if st != OK:
+        _raise(st, "nffacl_extract_keys_frames_device")
+
+
 def extract_keys_host(ptrs: np.ndarray, lens: np.ndarray, flags: int = 0, key6_cap: int | None = None):
     """nffacl_extract_keys_host: frame addresses (uint64[n], Batcher.frame_pointers)
     and lengths (uint32[n]) -> (keys KEY_DTYPE[n], key6 KEY6_DTYPE[n_key6]),
@@ -584,6 +598,15 @@ def route_plan(n: int, n_out: int):
     st = _route_plan(n, n_out, ctypes.byref(tiles), ctypes.byref(scratch))
     if st != OK:
         _raise(st, "nffacl_route_plan")
+    return tiles.value, scratch.value
+
+
+def route_frames_plan(m: int):
+    """nffacl_route_frames_plan: (tiles, scratch bytes) of gathering m packed frames."""
+    tiles, scratch = _u64(), _u64()
+    st = _route_frames_plan(m, ctypes.byref(tiles), ctypes.byref(scratch))
+    if st != OK:
+        _raise(st, "nffacl_route_frames_plan")
     return tiles.value, scratch.value
 
 
@@ -635,6 +658,18 @@ class Router:
         st = _route_gather(_ptr(slots), stride, _ptr(index), m, _ptr(out), s)
         if st != OK:
             _raise(st, "nffacl_route_gather_device")
+
+    def gather_frames(self, frames, desc, n: int, index, m: int, out, out_cap: int, out_desc, out_bytes,
+                      align: int = 64, stream=None):
+        """Output frame j <- frame index[j] of the packed batch (frames, desc[0..n)),
+        j < m, packed at `align`-byte rooms into out[0..out_cap) with descriptors
+        out_desc[m] (uint64, offset << 16 | len) and the bytes needed in
+        out_bytes[0] (uint64); device buffers.  Asynchronous on `stream`."""
+        s = stream.cuda_stream if hasattr(stream, "cuda_stream") else stream
+        st = _route_gather_frames(self._h, _ptr(frames), _ptr(desc), n, _ptr(index), m, align, _ptr(out), out_cap,
+                                  _ptr(out_desc), _ptr(out_bytes), s)
+        if st != OK:
+            _raise(st, "nffacl_route_gather_frames_device")
 
 
 class Batcher:
