@@ -22,6 +22,9 @@
  *                                  packets resident in HBM
  *   nffacl_classify_frames_device  same, over packed variable-length frames (IMIX)
  *   nffacl_extract_keys_frames_device  the same parse over packed frames, into 16-byte keys
+ *   nffacl_extract_keys_encap_frames_device <- the decapsulation that precedes it for tunnelled
+ *                                  traffic (vlan.go, mpls.go, gre.go, gtp.go:132-140): keys of the
+ *                                  inner headers, the frames left as they are
  *   nffacl_route_gather_frames_device <- the per-output packet slices of segmentProcess
  *                                  (flow/flow.go:1462-1486) as packed frames with
  *                                  descriptors, gathered through a route's index lists
@@ -410,6 +413,62 @@ NFFACL_API int nffacl_extract_keys_host(const uint8_t *const *frames, const uint
  * read by the kernel where they lie, pageable ones are staged.  Synchronous. */
 NFFACL_API int nffacl_classify_keys_host(nffacl_engine *eng, const nffacl_key *h_keys, const nffacl_key6 *h_key6,
                                          uint32_t n_key6, uint64_t n, uint32_t *h_port, uint8_t *h_permit);
+
+/* ---- keys of encapsulated frames (additive to ABI 7) ----------------------
+ *
+ * The traffic the reference decapsulates on the CPU before it classifies the
+ * inner 5-tuple (vlan.go, mpls.go: ParseL3CheckMPLS / RemoveMPLS, gre.go,
+ * gtp.go: DecapsulateIPv4GTP), resolved at extraction time instead: the key is
+ * that of the inner header, the frame is not rewritten, and every key call
+ * downstream works unchanged.
+ *
+ * Layers are resolved outermost-in, each only if its flag is set and it is
+ * present; resolution stops at the first layer that is not enabled.  The
+ * cursor is the offset of the L3 header and starts at 14:
+ *  1. VLAN: while the EtherType at cursor-2 is 0x8100 or 0x88A8 and fewer than
+ *     2 tags were taken, cursor += 4.
+ *  2. MPLS: if that EtherType is 0x8847, labels of 4 bytes are skipped through
+ *     the first with the S bit; more than 8 is malformed.  The reference leaves
+ *     label -> protocol to the caller; here the usual rule holds: the version
+ *     nibble of the next byte gives the family (4, 6, anything else family 0).
+ *  3. One tunnel level, if the L3 header at the cursor is IPv4 (any IHL >= 5)
+ *     or a fixed 40-byte IPv6 header (no extension headers) that carries
+ *     - GRE: protocol 47, version 0; 4 bytes plus 4 for each of the C, K and S
+ *       bits; NextProto 0x0800 / 0x86DD is the inner family, else family 0;
+ *     - GTP-U: UDP to port 2152, GTPv1, PT 1, message type 255; 8 bytes, 12
+ *       with any of E / S / PN; with E the extension headers are walked
+ *       (length in 4-octet units, 0 is malformed, next type in the last octet,
+ *       at most 4); the family is the version nibble.  For the frames
+ *       DecapsulateIPv4GTP handles this is its IPv4MinLen + UDPLen + GTPMinLen.
+ * The key is what nffacl_extract_keys_frames_device(flags = 0) gives for the
+ * frame with bytes [14, cursor) removed and the EtherType set to the resolved
+ * family: ports from wherever the inner IHL puts them, ports for ICMP, bytes
+ * past the length as 0.  A frame that matches nothing enabled gets its plain
+ * key (cursor 14, whatever its length), so encap = 0 is the plain call and
+ * mixed traffic needs no sorting.  A malformed frame — a cap exceeded, a GTP
+ * extension of length 0, or shims resolved up to or past the frame's end
+ * (cursor > 14 and cursor >= length) — gets the all-zero key (family 0,
+ * verdict 0).  Bytes past the length read as 0 during resolution too: a
+ * frame cut before a field that identifies a layer does not carry that layer. */
+enum nffacl_encap_flags {
+    NFFACL_ENCAP_VLAN = 1u,   /* up to 2 stacked tags, TPID 0x8100 or 0x88A8, 4 bytes each (vlan.go:66-76) */
+    NFFACL_ENCAP_MPLS = 2u,   /* EtherType 0x8847: labels of 4 bytes up to the bottom-of-stack bit
+                                 (mpls.go:38-41, 65-74), at most 8 */
+    NFFACL_ENCAP_GRE  = 4u,   /* IPv4 or IPv6 outer, protocol 47, GRE version 0 (gre.go:13-16) */
+    NFFACL_ENCAP_GTPU = 8u    /* IPv4 or IPv6 outer, UDP dport 2152, GTPv1, PT = 1, message type 255
+                                 (gtp.go:19-28, 62-64, 132-140) */
+};
+/* d_keys[i] <- the inner key of frame i under `encap` (nffacl_encap_flags).
+ * Frames, descriptors, alignment, key6 placement (d_key6[i], index i in the
+ * key), n < 2^32 and asynchrony as nffacl_extract_keys_frames_device; nothing
+ * outside a frame's 16-byte chunks is read.  d_inner_off (may be NULL; 2-byte
+ * aligned) gets the cursor of frame i — 14 for an unencapsulated frame — or
+ * 0xFFFF for a malformed one.  NFFACL_ERR_INVALID_ARG for unknown encap bits,
+ * NULL or misaligned buffers, n >= 2^32.  No atomics, no allocation: launches
+ * may be captured and replayed freely. */
+NFFACL_API int nffacl_extract_keys_encap_frames_device(const uint8_t *d_frames, const uint64_t *d_desc, uint64_t n,
+                                                       uint32_t encap, nffacl_key *d_keys, nffacl_key6 *d_key6,
+                                                       uint16_t *d_inner_off, void *stream);
 
 /* ---- burst aggregator (host ingest) ----------------
  *

@@ -38,8 +38,6 @@
 namespace nffacl {
 namespace dev {
 
-constexpr uint32_t kFam4 = 4u, kFam6 = 6u;
-
 // Key idx of the array, this lane's; lanes past n read the zero block (a key
 // of family 0: verdict 0), so the load needs no branch.
 __device__ __forceinline__ u32x4 load_key(const u32x4 *__restrict__ keys, uint64_t idx, uint64_t n) {
@@ -183,21 +181,6 @@ k_keys(const u32x4 *__restrict__ keys, const u32x4 *__restrict__ key6, uint32_t 
     // nontemporal verdict stores where the table should keep L2 (devutil.hpp store_port)
     key_batches<U, TM == kTabFlatLdsP>(keys, key6, n_key6, n, port_out, permit_out,
                                                     [&](const Fields &f) { return walk_key<NS, TM>(a, f, lane); });
-}
-
-// Packet idx's key from its parsed fields: each lane writes its own 16-byte
-// key (lane-contiguous dwordx4 stores), IPv6 lanes their 32-byte record at
-// their packet's index.
-__device__ __forceinline__ void store_key(const Fields &f, uint64_t idx, bool live, u32x4 *__restrict__ keys,
-                                          u32x4 *__restrict__ key6) {
-    u32x4 k = {0u, 0u, 0u, 0u};  // neither family: the zero key
-    if (f.is4) k = u32x4{f.s[0], f.t[0], f.ports, (f.proto & 0xFFu) | kFam4 << 8};
-    if (f.is6) k = u32x4{static_cast<uint32_t>(idx), 0u, f.ports, (f.proto & 0xFFu) | kFam6 << 8};
-    if (live) keys[idx] = k;
-    if (f.is6) {  // (is6 implies live)
-        key6[2 * idx] = u32x4{f.s[0], f.s[1], f.s[2], f.s[3]};
-        key6[2 * idx + 1] = u32x4{f.t[0], f.t[1], f.t[2], f.t[3]};
-    }
 }
 
 // Slots -> keys.  Dense 64-byte slots load lane-contiguous (devutil.hpp

@@ -57,6 +57,8 @@ ERR_TIMEOUT = -105
 
 ALGO_AUTO, ALGO_LINEAR, ALGO_INDEXED, ALGO_HYBRID = 0, 1, 2, 3
 PARSE_VLAN = 1  # ParseAllKnownL3CheckVLAN (packet/vlan.go:104-117) instead of ParseAllKnownL3
+# nffacl_encap_flags: the layers extract_keys_encap_frames_device resolves down to the inner 5-tuple
+ENCAP_VLAN, ENCAP_MPLS, ENCAP_GRE, ENCAP_GTPU = 1, 2, 4, 8
 
 # ---- record layouts ------------------------------------------------------------
 _L4 = [("id", "u1"), ("id_mask", "u1"), ("valid", "u1"), ("reserved", "u1"),
@@ -168,6 +170,7 @@ _route_gather_frames = _sig("nffacl_route_gather_frames_device", _i, _vp, _vp, _
 _classify_keys_device = _sig("nffacl_classify_keys_device", _i, _vp, _vp, _vp, _u32, _u64, _vp, _vp, _vp)
 _extract_keys_device = _sig("nffacl_extract_keys_device", _i, _vp, _u32, _u64, _u32, _vp, _vp, _vp)
 _extract_keys_frames = _sig("nffacl_extract_keys_frames_device", _i, _vp, _vp, _u64, _u32, _vp, _vp, _vp)
+_extract_keys_encap = _sig("nffacl_extract_keys_encap_frames_device", _i, _vp, _vp, _u64, _u32, _vp, _vp, _vp, _vp)
 _extract_keys_host = _sig("nffacl_extract_keys_host", _i, _vp, _vp, _u64, _u32, _vp, _vp, _u64, ctypes.POINTER(_u64))
 _classify_keys_host = _sig("nffacl_classify_keys_host", _i, _vp, _vp, _vp, _u32, _u64, _vp, _vp)
 
@@ -226,6 +229,7 @@ EXPORTED_SYMBOLS = [
     "nffacl_router_destroy", "nffacl_classify_keys_device", "nffacl_extract_keys_device",
     "nffacl_extract_keys_host", "nffacl_classify_keys_host", "nffacl_route_frames_plan",
     "nffacl_route_gather_frames_device", "nffacl_extract_keys_frames_device",
+    "nffacl_extract_keys_encap_frames_device",
 ]
 
 
@@ -571,6 +575,17 @@ def extract_keys_frames_device(frames, desc, n: int, keys, key6, flags: int = 0,
     st = _extract_keys_frames(_ptr(frames), _ptr(desc), n, flags, _ptr(keys), _ptr(key6), s)
     if st != OK:
         _raise(st, "nffacl_extract_keys_frames_device")
+
+
+def extract_keys_encap_frames_device(frames, desc, n: int, keys, key6, encap: int, inner_off=None, stream=None):
+    """nffacl_extract_keys_encap_frames_device: keys[i] <- the key of packed
+    frame i's inner header under the ENCAP_* layers of `encap` (an IPv6 record
+    to key6[i]); inner_off (uint16[n] on the device, optional) gets each inner
+    L3 header's offset, 0xFFFF for a malformed frame."""
+    s = stream.cuda_stream if hasattr(stream, "cuda_stream") else stream
+    st = _extract_keys_encap(_ptr(frames), _ptr(desc), n, encap, _ptr(keys), _ptr(key6), _ptr(inner_off), s)
+    if st != OK:
+        _raise(st, "nffacl_extract_keys_encap_frames_device")
 
 
 def extract_keys_host(ptrs: np.ndarray, lens: np.ndarray, flags: int = 0, key6_cap: int | None = None):
