@@ -28,6 +28,8 @@
  *   nffacl_route_gather_frames_device <- the per-output packet slices of segmentProcess
  *                                  (flow/flow.go:1462-1486) as packed frames with
  *                                  descriptors, gathered through a route's index lists
+ *   nffacl_route_gather_decap_frames_device <- the same with RemoveVLANTag / RemoveMPLS /
+ *                                  DecapsulateIPv4GTP (packet.go:789-798) done on the way
  *   nffacl_classify_host        <- the VectorSeparateFunction body the reference runs per
  *                                  burst (flow/flow.go:131, 1487-1520;
  *                                  test/stability/testSingleWorkingFF/testSingleWorkingFF.go:538-546)
@@ -794,7 +796,48 @@ NFFACL_API int nffacl_route_gather_frames_device(nffacl_router *r, const uint8_t
                                                  uint64_t n, const uint32_t *d_index, uint64_t m, uint32_t align,
                                                  uint8_t *d_out, uint64_t out_cap, uint64_t *d_out_desc,
                                                  uint64_t *d_out_bytes, void *stream);
-/* Its plan (pure, no device): tiles = ceil(m / frames-per-tile);
+/* The same gather, decapsulating on the way (additive to ABI 7): what the
+ * reference's users do between classifying the inner header and the enqueue —
+ * RemoveVLANTag, RemoveMPLS, DecapsulateIPv4GTP (gtp.go:132-140), i.e.
+ * DecapsulateHead(EtherLen, length) (packet.go:789-798), which drops the bytes
+ * [14, 14 + length) and keeps the Ethernet header in front of the payload.
+ * d_inner_off[0..n) and d_keys[0..n) are what
+ * nffacl_extract_keys_encap_frames_device wrote for (d_frames, d_desc); both
+ * are required (NULL, d_inner_off not 2-byte or d_keys not 16-byte aligned:
+ * NFFACL_ERR_INVALID_ARG).  Of a key only the `meta` dword is read.
+ * For source frame i = d_index[j] < n of length L and cursor c = d_inner_off[i]:
+ *   strip   s = c - 14 if 14 < c < L and (c - 14) % 4 == 0, else s = 0: an
+ *           unencapsulated frame (14), a malformed one (0xFFFF) and any value
+ *           the extraction does not produce are copied whole, and a bad cursor
+ *           never makes the call read outside the frame
+ *   length  L' = L - s; d_out_desc[j] = off_j << 16 | L'; the room is L'
+ *           rounded up to `align`, pads zeroed
+ *   bytes   [0, 12) the source's; [12, 14) the EtherType E, big-endian;
+ *           [14, L') source bytes [14 + s, L)
+ *   E       s == 0: the source's bytes 12-13 (the frame is bit-identical to
+ *           what nffacl_route_gather_frames_device writes); else by the family
+ *           in d_keys[i].meta: 4 -> 0x0800, 6 -> 0x86DD, any other -> source
+ *           bytes [c - 2, c).  Those are the inner EtherType behind VLAN tags
+ *           and the NextProto of an option-less GRE header; behind an MPLS
+ *           stack or a GRE header with options they are NOT an EtherType (the
+ *           end of the last label, of the last option).  Such frames have
+ *           family 0 and get verdict 0 whatever E says.
+ * For every frame the extraction did not mark malformed,
+ * nffacl_extract_keys_frames_device(flags = 0) on (d_out, d_out_desc) gives
+ * the key nffacl_extract_keys_encap_frames_device gave for the source frame.
+ * Everything else — packing, align, out_cap, *d_out_bytes, the empty frame for
+ * d_index[j] >= n, repeated indices, m <= max_n, m = 0, three launches, no
+ * allocation, the router's event and one-stream rule, alignment of d_frames
+ * and d_out, a 16-byte source chunk read only if it starts inside its frame —
+ * is as nffacl_route_gather_frames_device; the scratch is the same
+ * (nffacl_route_frames_plan). */
+NFFACL_API int nffacl_route_gather_decap_frames_device(nffacl_router *r, const uint8_t *d_frames,
+                                                       const uint64_t *d_desc, uint64_t n,
+                                                       const uint16_t *d_inner_off, const nffacl_key *d_keys,
+                                                       const uint32_t *d_index, uint64_t m, uint32_t align,
+                                                       uint8_t *d_out, uint64_t out_cap, uint64_t *d_out_desc,
+                                                       uint64_t *d_out_bytes, void *stream);
+/* Their plan (pure, no device): tiles = ceil(m / frames-per-tile);
  * scratch_bytes = what a router of max_n = m holds for this path (one 64-bit
  * sum per tile).  NFFACL_ERR_INVALID_ARG for m > 2^31 or NULL outputs. */
 NFFACL_API int nffacl_route_frames_plan(uint64_t m, uint64_t *tiles, uint64_t *scratch_bytes);

@@ -61,6 +61,25 @@ __device__ __forceinline__ uint32_t wave_scan_incl(uint32_t x) {
     return x;
 }
 
+// The packed-frame gathers (route_frames.hip, route_decap.hip).  Position j's
+// frame: its descriptor (0: an empty frame, for j >= m and for an index past
+// the batch) and its room in chunks.  `amask` = align - 1.
+__device__ __forceinline__ uint64_t frame_at(const uint64_t *__restrict__ desc, uint64_t n,
+                                             const uint32_t *__restrict__ index, uint64_t j, uint64_t m,
+                                             uint32_t amask, uint32_t &room) {
+    uint64_t ds = 0;
+    if (j < m) {
+        const uint32_t i = index[j];
+        if (i < n) ds = desc[i];
+    }
+    room = (((static_cast<uint32_t>(ds) & 0xFFFFu) + amask) & ~amask) >> 4;  // <= 4096
+    return ds;
+}
+
+// Defined in route_frames.hip; the decapsulating gather (route_decap.hip) launches it too.
+__global__ __launch_bounds__(kRouteBlock) void k_gatherf_scan(uint64_t *sums, uint32_t tiles,
+                                                              uint64_t *__restrict__ out_bytes);
+
 }  // namespace dev
 
 }  // namespace nffacl

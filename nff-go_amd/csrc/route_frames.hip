@@ -38,20 +38,6 @@ namespace dev {
 
 constexpr uint32_t kWaves = kRouteBlock / 64;
 
-// Position j's frame: its descriptor (0: an empty frame, for j >= m and for
-// an index past the batch) and its room in chunks.  `amask` = align - 1.
-__device__ __forceinline__ uint64_t frame_at(const uint64_t *__restrict__ desc, uint64_t n,
-                                             const uint32_t *__restrict__ index, uint64_t j, uint64_t m,
-                                             uint32_t amask, uint32_t &room) {
-    uint64_t ds = 0;
-    if (j < m) {
-        const uint32_t i = index[j];
-        if (i < n) ds = desc[i];
-    }
-    room = (((static_cast<uint32_t>(ds) & 0xFFFFu) + amask) & ~amask) >> 4;  // <= 4096
-    return ds;
-}
-
 // A tile's rooms fit 22 bits (1024 frames x 4096 chunks): summed in u32.
 __global__ __launch_bounds__(kRouteBlock) void k_gatherf_sums(const uint64_t *__restrict__ desc, uint64_t n,
                                                               const uint32_t *__restrict__ index, uint64_t m,

@@ -167,6 +167,8 @@ _router_destroy = _sig("nffacl_router_destroy", None, _vp)
 _route_frames_plan = _sig("nffacl_route_frames_plan", _i, _u64, ctypes.POINTER(_u64), ctypes.POINTER(_u64))
 _route_gather_frames = _sig("nffacl_route_gather_frames_device", _i, _vp, _vp, _vp, _u64, _vp, _u64, _u32, _vp, _u64,
                             _vp, _vp, _vp)
+_route_gather_decap = _sig("nffacl_route_gather_decap_frames_device", _i, _vp, _vp, _vp, _u64, _vp, _vp, _vp, _u64, _u32,
+                           _vp, _u64, _vp, _vp, _vp)
 _classify_keys_device = _sig("nffacl_classify_keys_device", _i, _vp, _vp, _vp, _u32, _u64, _vp, _vp, _vp)
 _extract_keys_device = _sig("nffacl_extract_keys_device", _i, _vp, _u32, _u64, _u32, _vp, _vp, _vp)
 _extract_keys_frames = _sig("nffacl_extract_keys_frames_device", _i, _vp, _vp, _u64, _u32, _vp, _vp, _vp)
@@ -229,7 +231,7 @@ EXPORTED_SYMBOLS = [
     "nffacl_router_destroy", "nffacl_classify_keys_device", "nffacl_extract_keys_device",
     "nffacl_extract_keys_host", "nffacl_classify_keys_host", "nffacl_route_frames_plan",
     "nffacl_route_gather_frames_device", "nffacl_extract_keys_frames_device",
-    "nffacl_extract_keys_encap_frames_device",
+    "nffacl_extract_keys_encap_frames_device", "nffacl_route_gather_decap_frames_device",
 ]
 
 
@@ -685,6 +687,21 @@ class Router:
                                   _ptr(out_desc), _ptr(out_bytes), s)
         if st != OK:
             _raise(st, "nffacl_route_gather_frames_device")
+
+    def gather_decap_frames(self, frames, desc, n: int, inner_off, keys, index, m: int, out, out_cap: int, out_desc,
+                            out_bytes, align: int = 64, stream=None):
+        """gather_frames that drops each frame's shims on the way: inner_off
+        (uint16[n]) and keys (KEY_DTYPE[n]) are what
+        extract_keys_encap_frames_device wrote for (frames, desc); output frame
+        j is frame index[j] without its bytes [14, inner_off), its EtherType
+        set by the key's family, out_desc[j] = offset << 16 | the shorter
+        length.  Frames whose cursor is 14, 0xFFFF or otherwise unusable are
+        copied whole.  Asynchronous on `stream`."""
+        s = stream.cuda_stream if hasattr(stream, "cuda_stream") else stream
+        st = _route_gather_decap(self._h, _ptr(frames), _ptr(desc), n, _ptr(inner_off), _ptr(keys), _ptr(index), m,
+                                 align, _ptr(out), out_cap, _ptr(out_desc), _ptr(out_bytes), s)
+        if st != OK:
+            _raise(st, "nffacl_route_gather_decap_frames_device")
 
 
 class Batcher:
