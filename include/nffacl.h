@@ -30,6 +30,9 @@
  *                                  descriptors, gathered through a route's index lists
  *   nffacl_route_gather_decap_frames_device <- the same with RemoveVLANTag / RemoveMPLS /
  *                                  DecapsulateIPv4GTP (packet.go:789-798) done on the way
+ *   nffacl_checksum_frames_device <- CalculateIPv4Checksum, CalculateIPv{4,6}{TCP,UDP,ICMP}Checksum
+ *                                  (packet/checksum.go:186-345) over packed frames, each
+ *                                  compared with the field the frame carries
  *   nffacl_classify_host        <- the VectorSeparateFunction body the reference runs per
  *                                  burst (flow/flow.go:131, 1487-1520;
  *                                  test/stability/testSingleWorkingFF/testSingleWorkingFF.go:538-546)
@@ -471,6 +474,82 @@ enum nffacl_encap_flags {
 NFFACL_API int nffacl_extract_keys_encap_frames_device(const uint8_t *d_frames, const uint64_t *d_desc, uint64_t n,
                                                        uint32_t encap, nffacl_key *d_keys, nffacl_key6 *d_key6,
                                                        uint16_t *d_inner_off, void *stream);
+
+/* ---- checksums of packed frames (additive to ABI 7) -----------------------
+ *
+ * What packet/checksum.go computes per packet on the CPU, and what the NIC's
+ * RX offload checks on the reference's own path, for a batch that stays in
+ * HBM: the IPv4 header sum and the TCP / UDP / ICMP sum of every frame, each
+ * compared with the field the frame carries.  Frames are not written.
+ *
+ * Per frame: L is its length; c is the cursor, 14 if d_inner_off is NULL,
+ * else d_inner_off[i] as nffacl_extract_keys_encap_frames_device writes it.
+ * Bytes are on the wire, "words" are big-endian 16-bit words, fold is
+ * reduceChecksum (checksum.go:179-184).
+ *
+ * Family.  c odd (0xFFFF is), c < 14 or c >= L: the all-zero record.  c == 14:
+ * EtherType 0x0800 is IPv4, 0x86DD IPv6, anything else the all-zero record,
+ * and the version nibble at byte c must agree or the record is all zero.
+ * c > 14: the version nibble at byte c decides (4, 6, else all zero), the rule
+ * of the encap call below MPLS and GTP-U.
+ *
+ * IPv4 header.  H = 4 * IHL.  IHL < 5, c + 20 > L or c + H > L: the record is
+ * LENGTH only.  Under NFFACL_CK_IP4, ip = ~fold(words of [c, c + H) with the
+ * checksum field as 0) — options count, which CalculateIPv4Checksum ignores —
+ * and IP4_DONE is set; IP4_BAD if the stored field differs, 0x0000 and 0xFFFF
+ * comparing equal.
+ *
+ * IPv4 L4, under NFFACL_CK_L4.  T is TotalLength.  T < H or c + T > L: LENGTH.
+ * Otherwise, any of bits 0x3FFF of the word at c + 6 (MF, fragment offset):
+ * FRAGMENT.  Otherwise the protocol must be 6, 17 or 1, or nothing is
+ * computed.  The span is [c + H, c + T), m = T - H bytes; Ethernet padding past
+ * T is not part of it.  m below 20 (TCP) or 8 (UDP, ICMP), or a UDP DgramLen
+ * other than m: LENGTH.  Otherwise l4 = ~fold(words of the span, an odd last
+ * byte padded with 0 on the right, its checksum field (offset 16 TCP, 6 UDP,
+ * 2 ICMP) as 0, plus the pseudo-header: the source and destination words, the
+ * protocol and m; none for ICMP), for UDP a result of 0 becomes 0xFFFF, and
+ * L4_DONE is set.  A UDP field stored as 0 sets L4_ABSENT and never L4_BAD;
+ * otherwise L4_BAD as for the header.
+ *
+ * IPv6 L4, under NFFACL_CK_L4 (an IPv6 frame's record is all zero without
+ * it).  The header is the fixed 40 bytes: c + 40 > L or c + 40 + PayloadLen > L
+ * is LENGTH.  The next header must be 6, 17 or 58 directly (an extension
+ * header means no L4 sum, as elsewhere in this library).  The span is
+ * [c + 40, c + 40 + PayloadLen), minimum lengths and DgramLen as for IPv4; the
+ * pseudo-header is the 16 address words, PayloadLen and the next header, for
+ * all three protocols.  A UDP field stored as 0 is L4_BAD.
+ *
+ * ip and l4 are host-order numbers, as the reference's functions return them:
+ * for well-formed IHL-5 packets they are what CalculateIPv4Checksum,
+ * CalculateIPv{4,6}{TCP,UDP}Checksum and CalculateIPv{4,6}ICMPChecksum return.
+ * Divergences: IPv4 options count, in the header sum and in where L4 starts
+ * (the reference subtracts IPv4MinLen whatever the IHL); lengths are checked
+ * against the frame (the reference sums whatever memory follows). */
+enum nffacl_cksum_what { NFFACL_CK_IP4 = 1u, NFFACL_CK_L4 = 2u };
+enum nffacl_cksum_status {
+    NFFACL_CK_IP4_DONE = 1u,  NFFACL_CK_IP4_BAD = 2u,
+    NFFACL_CK_L4_DONE  = 4u,  NFFACL_CK_L4_BAD  = 8u,
+    NFFACL_CK_L4_ABSENT = 16u, /* UDP over IPv4 sent without a checksum (field 0): computed, never BAD */
+    NFFACL_CK_FRAGMENT  = 32u, /* IPv4 MF set or fragment offset != 0: no L4 sum */
+    NFFACL_CK_LENGTH    = 64u  /* a header or a length field claims bytes the frame does not have,
+                                  or is below its minimum: what depends on it is not computed */
+};
+typedef struct nffacl_cksum { uint16_t ip; uint16_t l4; uint32_t status; } nffacl_cksum; /* 8 bytes, arrays 8-byte aligned */
+/* d_sums[i] (may be NULL) <- frame i's record, every frame's written, zero
+ * where nothing applies; bit i of d_bad_bits (may be NULL; ceil(n / 64) words,
+ * the last word's spare bits 0) <- IP4_BAD | L4_BAD of it.  `what` is a
+ * non-empty set of nffacl_cksum_what.  Frames, descriptors, alignment,
+ * n < 2^32 and asynchrony as nffacl_extract_keys_frames_device; d_inner_off
+ * is 2-byte aligned; nothing outside a frame's 16-byte chunks is read.  No
+ * global atomics, no allocation, no scratch: launches may be captured and
+ * replayed freely.  NFFACL_ERR_INVALID_ARG, with no launch, for unknown `what`
+ * bits or what == 0, both outputs NULL, NULL or misaligned buffers,
+ * n >= 2^32. */
+NFFACL_API int nffacl_checksum_frames_device(const uint8_t *d_frames, const uint64_t *d_desc, uint64_t n,
+                                             const uint16_t *d_inner_off, uint32_t what, nffacl_cksum *d_sums,
+                                             uint64_t *d_bad_bits, void *stream);
+/* Pure, no device: *tiles >= 1, a workgroup's tile is ceil(n / tiles) frames. */
+NFFACL_API int nffacl_checksum_frames_plan(uint64_t n, uint64_t *tiles);
 
 /* ---- burst aggregator (host ingest) ----------------
  *

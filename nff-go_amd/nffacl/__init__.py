@@ -59,6 +59,9 @@ ALGO_AUTO, ALGO_LINEAR, ALGO_INDEXED, ALGO_HYBRID = 0, 1, 2, 3
 PARSE_VLAN = 1  # ParseAllKnownL3CheckVLAN (packet/vlan.go:104-117) instead of ParseAllKnownL3
 # nffacl_encap_flags: the layers extract_keys_encap_frames_device resolves down to the inner 5-tuple
 ENCAP_VLAN, ENCAP_MPLS, ENCAP_GRE, ENCAP_GTPU = 1, 2, 4, 8
+# nffacl_cksum_what / nffacl_cksum_status: what checksum_frames_device computes, and a record's status bits
+CK_IP4, CK_L4 = 1, 2
+CK_IP4_DONE, CK_IP4_BAD, CK_L4_DONE, CK_L4_BAD, CK_L4_ABSENT, CK_FRAGMENT, CK_LENGTH = 1, 2, 4, 8, 16, 32, 64
 
 # ---- record layouts ------------------------------------------------------------
 _L4 = [("id", "u1"), ("id_mask", "u1"), ("valid", "u1"), ("reserved", "u1"),
@@ -173,6 +176,8 @@ _classify_keys_device = _sig("nffacl_classify_keys_device", _i, _vp, _vp, _vp, _
 _extract_keys_device = _sig("nffacl_extract_keys_device", _i, _vp, _u32, _u64, _u32, _vp, _vp, _vp)
 _extract_keys_frames = _sig("nffacl_extract_keys_frames_device", _i, _vp, _vp, _u64, _u32, _vp, _vp, _vp)
 _extract_keys_encap = _sig("nffacl_extract_keys_encap_frames_device", _i, _vp, _vp, _u64, _u32, _vp, _vp, _vp, _vp)
+_checksum_frames = _sig("nffacl_checksum_frames_device", _i, _vp, _vp, _u64, _vp, _u32, _vp, _vp, _vp)
+_checksum_frames_plan = _sig("nffacl_checksum_frames_plan", _i, _u64, ctypes.POINTER(_u64))
 _extract_keys_host = _sig("nffacl_extract_keys_host", _i, _vp, _vp, _u64, _u32, _vp, _vp, _u64, ctypes.POINTER(_u64))
 _classify_keys_host = _sig("nffacl_classify_keys_host", _i, _vp, _vp, _vp, _u32, _u64, _vp, _vp)
 
@@ -180,6 +185,9 @@ _classify_keys_host = _sig("nffacl_classify_keys_host", _i, _vp, _vp, _vp, _u32,
 KEY_DTYPE = np.dtype([("a", "<u4"), ("b", "<u4"), ("ports", "<u4"), ("meta", "<u4")])
 KEY6_DTYPE = np.dtype([("src", "u1", 16), ("dst", "u1", 16)])
 assert KEY_DTYPE.itemsize == 16 and KEY6_DTYPE.itemsize == 32
+# nffacl_cksum: one frame's checksums (host-order numbers) and CK_* status bits
+CKSUM_DTYPE = np.dtype([("ip", "<u2"), ("l4", "<u2"), ("status", "<u4")])
+assert CKSUM_DTYPE.itemsize == 8
 
 
 class KernelInfo(ctypes.Structure):
@@ -232,6 +240,7 @@ EXPORTED_SYMBOLS = [
     "nffacl_extract_keys_host", "nffacl_classify_keys_host", "nffacl_route_frames_plan",
     "nffacl_route_gather_frames_device", "nffacl_extract_keys_frames_device",
     "nffacl_extract_keys_encap_frames_device", "nffacl_route_gather_decap_frames_device",
+    "nffacl_checksum_frames_device", "nffacl_checksum_frames_plan",
 ]
 
 
@@ -588,6 +597,27 @@ def extract_keys_encap_frames_device(frames, desc, n: int, keys, key6, encap: in
     st = _extract_keys_encap(_ptr(frames), _ptr(desc), n, encap, _ptr(keys), _ptr(key6), _ptr(inner_off), s)
     if st != OK:
         _raise(st, "nffacl_extract_keys_encap_frames_device")
+
+
+def checksum_frames_device(frames, desc, n: int, sums, bad_bits=None, inner_off=None, what: int = CK_IP4 | CK_L4,
+                           stream=None):
+    """nffacl_checksum_frames_device: sums[i] (CKSUM_DTYPE, 8 bytes a record, optional) <- the IPv4 header and
+    TCP / UDP / ICMP checksums of packed frame i under the CK_* bits of `what` and its status; bit i of
+    bad_bits (uint64[ceil(n / 64)], optional) <- a stored checksum differs.  inner_off (uint16[n], optional):
+    the L3 offsets extract_keys_encap_frames_device wrote, else 14."""
+    s = stream.cuda_stream if hasattr(stream, "cuda_stream") else stream
+    st = _checksum_frames(_ptr(frames), _ptr(desc), n, _ptr(inner_off), what, _ptr(sums), _ptr(bad_bits), s)
+    if st != OK:
+        _raise(st, "nffacl_checksum_frames_device")
+
+
+def checksum_frames_plan(n: int) -> int:
+    """nffacl_checksum_frames_plan: the tiles of n frames (a tile is ceil(n / tiles) frames)."""
+    tiles = _u64()
+    st = _checksum_frames_plan(n, ctypes.byref(tiles))
+    if st != OK:
+        _raise(st, "nffacl_checksum_frames_plan")
+    return tiles.value
 
 
 def extract_keys_host(ptrs: np.ndarray, lens: np.ndarray, flags: int = 0, key6_cap: int | None = None):
