@@ -924,6 +924,88 @@ NFFACL_API int nffacl_route_frames_plan(uint64_t m, uint64_t *tiles, uint64_t *s
  * synchronise), then frees. */
 NFFACL_API void nffacl_router_destroy(nffacl_router *r);
 
+/* ---- longest-prefix-match next hops -----------------------------------------
+ * CreateLPM / (*LPM).Add / Delete / Lookup / Free (packet/packet.go:857-912,
+ * DPDK's rte_lpm): the route table between a key's destination address and
+ * nffacl_route_device, for a batch resident in HBM.  Additive to ABI 7.
+ *
+ * The prefix of a rule is the top `depth` bits of the u32 value, exactly as
+ * Lookup computes ip >> 8.  The reference is handed ipv4.DstAddr as it lies in
+ * the header (a types.IPv4Address, first octet in the low byte), so it counts
+ * bits from the LAST octet; that is the default here too.
+ * NFFACL_LPM_SWAP_BYTES byte-swaps each looked-up address before the walk, so
+ * that a types.IPv4Address out of a key is matched from its first octet
+ * against rules given as host-order numbers.
+ *
+ * Divergence: the reference's Add / Delete are visible to the next Lookup.
+ * Here they change the host rule list only; nffacl_lpm_commit compiles the
+ * list from scratch into a device table and makes it the active one, and a
+ * lookup uses the table of the last commit (examples/netlink.go updates its
+ * table in batches anyway).  A retired table is freed stream-ordered behind
+ * the launches that still read it, with no device synchronise.
+ *
+ * The device table is not DIR-24-8 but 16-8-8: 65 536 u16 top-level entries
+ * that a workgroup stages into LDS (a leaf names one of up to 4 095 next hops
+ * held beside them), and 256-entry groups in HBM for prefixes longer than 16
+ * and 24.  A table whose level-1 groups (a /16 block holding a longer prefix,
+ * or a /16 leaf past the 4 095 coded hops) outnumber 65 535 - H, H the coded
+ * hops, does not commit: NFFACL_ERR_NOMEM.
+ *
+ * Thread-safe: the rule list and the active table are guarded by one lock;
+ * lookups may run concurrently with add / delete / commit. */
+typedef struct nffacl_lpm nffacl_lpm;
+enum nffacl_lpm_flags {
+    NFFACL_LPM_SWAP_BYTES = 1u,   /* bswap32 every address before the walk */
+    NFFACL_LPM_FORCE_LDS = 2u,    /* the form that stages the top level in LDS, whatever n */
+    NFFACL_LPM_FORCE_GLOBAL = 4u  /* the form that reads it from global memory (not both) */
+};
+/* CreateLPM(name, socket, maxRules, numberTbl8); name and socket have no
+ * meaning here.  max_rules >= 1. */
+NFFACL_API int nffacl_lpm_create(uint32_t max_rules, uint32_t number_tbl8, nffacl_lpm **out);
+/* depth 1..32, else NFFACL_ERR_INVALID_ARG.  ip is masked to depth, next_hop
+ * keeps its low 24 bits (Lookup's & 0x00FFFFFF).  An existing (masked ip,
+ * depth) has its next hop replaced.  NFFACL_ERR_NOMEM when the rule count
+ * would pass max_rules, or the distinct /24 blocks holding a prefix longer
+ * than 24 would pass number_tbl8 (rte_lpm's tbl8 budget, checked here). */
+NFFACL_API int nffacl_lpm_add(nffacl_lpm *lpm, uint32_t ip, uint32_t depth, uint32_t next_hop);
+/* NFFACL_ERR_INVALID_ARG when (masked ip, depth) is not in the list. */
+NFFACL_API int nffacl_lpm_delete(nffacl_lpm *lpm, uint32_t ip, uint32_t depth);
+NFFACL_API int nffacl_lpm_count(const nffacl_lpm *lpm, uint64_t *rules);
+NFFACL_API void nffacl_lpm_free(nffacl_lpm *lpm);
+/* Compile the rule list and make the result the active table on hip_device
+ * (every commit of one nffacl_lpm names the same device). */
+NFFACL_API int nffacl_lpm_commit(nffacl_lpm *lpm, int hip_device);
+
+/* The compiled table without a device (tooling and tests).  Blob, in dwords:
+ * [0] magic  [1] H  [2] level-1 groups  [3] level-2 groups  [4] off_l0
+ * [5] off_hops  [6] off_l1  [7] off_l2.  L0: 65 536 u16 by address bits
+ * 31..16 (0 miss, 1..H leaf with answer word hops[e], above H level-1 group
+ * e - H - 1).  Answer and group words: bit 31 hit, bit 30 (level 1 only)
+ * level-2 group number in the low 24 bits, else the next hop there.  Groups
+ * are 256 words, level 1 by bits 15..8, level 2 by bits 7..0.  *need_dwords
+ * is always set; blob may be NULL; cap_dwords too small with a blob is
+ * NFFACL_ERR_INVALID_ARG. */
+NFFACL_API int nffacl_lpm_compile(const nffacl_lpm *lpm, uint32_t *blob, uint64_t cap_dwords,
+                                  uint64_t *need_dwords);
+
+/* d_next[i] (may be NULL) <- the next hop of d_addr[i], or miss_value on a
+ * miss; bit i of d_hit_bits (may be NULL; ceil(n / 64) words, the last word's
+ * spare bits 0) <- Lookup's bool.  d_next can go straight into
+ * nffacl_route_device.  Arrays 16-byte aligned, n < 2^32; nothing past n is
+ * read or written.  Asynchronous on `stream`; no atomics, no allocation, no
+ * memset: a launch may be captured and replayed while the table it was issued
+ * against is still the active one (a commit retires it).
+ * NFFACL_ERR_INVALID_ARG, with no launch: no commit yet, both outputs NULL,
+ * unknown flags or both FORCE flags, NULL or misaligned arrays, n >= 2^32. */
+NFFACL_API int nffacl_lpm_lookup_device(nffacl_lpm *lpm, const uint32_t *d_addr, uint64_t n, uint32_t flags,
+                                        uint32_t miss_value, uint32_t *d_next, uint64_t *d_hit_bits,
+                                        void *stream);
+/* The same for the b field (destination) of family-4 keys; a key of any other
+ * family misses, and nothing outside d_keys[0, n) is read. */
+NFFACL_API int nffacl_lpm_lookup_keys_device(nffacl_lpm *lpm, const nffacl_key *d_keys, uint64_t n,
+                                             uint32_t flags, uint32_t miss_value, uint32_t *d_next,
+                                             uint64_t *d_hit_bits, void *stream);
+
 /* ---- misc ------------------------------------------------------------- */
 NFFACL_API const char *nffacl_strerror(int status);
 NFFACL_API int nffacl_abi_version(void);

@@ -62,6 +62,8 @@ ENCAP_VLAN, ENCAP_MPLS, ENCAP_GRE, ENCAP_GTPU = 1, 2, 4, 8
 # nffacl_cksum_what / nffacl_cksum_status: what checksum_frames_device computes, and a record's status bits
 CK_IP4, CK_L4 = 1, 2
 CK_IP4_DONE, CK_IP4_BAD, CK_L4_DONE, CK_L4_BAD, CK_L4_ABSENT, CK_FRAGMENT, CK_LENGTH = 1, 2, 4, 8, 16, 32, 64
+# nffacl_lpm_flags: byte-swap every address before the walk; pick the lookup kernel's form
+LPM_SWAP_BYTES, LPM_FORCE_LDS, LPM_FORCE_GLOBAL = 1, 2, 4
 
 # ---- record layouts ------------------------------------------------------------
 _L4 = [("id", "u1"), ("id_mask", "u1"), ("valid", "u1"), ("reserved", "u1"),
@@ -178,6 +180,15 @@ _extract_keys_frames = _sig("nffacl_extract_keys_frames_device", _i, _vp, _vp, _
 _extract_keys_encap = _sig("nffacl_extract_keys_encap_frames_device", _i, _vp, _vp, _u64, _u32, _vp, _vp, _vp, _vp)
 _checksum_frames = _sig("nffacl_checksum_frames_device", _i, _vp, _vp, _u64, _vp, _u32, _vp, _vp, _vp)
 _checksum_frames_plan = _sig("nffacl_checksum_frames_plan", _i, _u64, ctypes.POINTER(_u64))
+_lpm_create = _sig("nffacl_lpm_create", _i, _u32, _u32, _pp)
+_lpm_add = _sig("nffacl_lpm_add", _i, _vp, _u32, _u32, _u32)
+_lpm_delete = _sig("nffacl_lpm_delete", _i, _vp, _u32, _u32)
+_lpm_count = _sig("nffacl_lpm_count", _i, _vp, ctypes.POINTER(_u64))
+_lpm_free = _sig("nffacl_lpm_free", None, _vp)
+_lpm_commit = _sig("nffacl_lpm_commit", _i, _vp, _i)
+_lpm_compile = _sig("nffacl_lpm_compile", _i, _vp, _vp, _u64, ctypes.POINTER(_u64))
+_lpm_lookup = _sig("nffacl_lpm_lookup_device", _i, _vp, _vp, _u64, _u32, _u32, _vp, _vp, _vp)
+_lpm_lookup_keys = _sig("nffacl_lpm_lookup_keys_device", _i, _vp, _vp, _u64, _u32, _u32, _vp, _vp, _vp)
 _extract_keys_host = _sig("nffacl_extract_keys_host", _i, _vp, _vp, _u64, _u32, _vp, _vp, _u64, ctypes.POINTER(_u64))
 _classify_keys_host = _sig("nffacl_classify_keys_host", _i, _vp, _vp, _vp, _u32, _u64, _vp, _vp)
 
@@ -241,6 +252,8 @@ EXPORTED_SYMBOLS = [
     "nffacl_route_gather_frames_device", "nffacl_extract_keys_frames_device",
     "nffacl_extract_keys_encap_frames_device", "nffacl_route_gather_decap_frames_device",
     "nffacl_checksum_frames_device", "nffacl_checksum_frames_plan",
+    "nffacl_lpm_create", "nffacl_lpm_add", "nffacl_lpm_delete", "nffacl_lpm_count", "nffacl_lpm_free",
+    "nffacl_lpm_commit", "nffacl_lpm_compile", "nffacl_lpm_lookup_device", "nffacl_lpm_lookup_keys_device",
 ]
 
 
@@ -634,6 +647,91 @@ def extract_keys_host(ptrs: np.ndarray, lens: np.ndarray, flags: int = 0, key6_c
     if st != OK:
         _raise(st, "nffacl_extract_keys_host")
     return keys, key6[:n6.value]
+
+
+class LPM:
+    """nffacl_lpm: the reference's LPM (packet/packet.go:857-912).  Add and
+    Delete return the status (0, or a negative ERR_*) as the reference's return
+    an int; they change the rule list only, and commit() compiles it into the
+    device table the lookups use."""
+
+    def __init__(self, max_rules: int, number_tbl8: int):
+        h = ctypes.c_void_p()
+        st = _lpm_create(max_rules, number_tbl8, ctypes.byref(h))
+        if st != OK:
+            _raise(st, "nffacl_lpm_create")
+        self._h = h
+
+    def Add(self, ip: int, depth: int, next_hop: int) -> int:
+        return _lpm_add(self._h, ip & 0xFFFFFFFF, depth, next_hop & 0xFFFFFFFF)
+
+    def Delete(self, ip: int, depth: int) -> int:
+        return _lpm_delete(self._h, ip & 0xFFFFFFFF, depth)
+
+    def count(self) -> int:
+        n = _u64()
+        st = _lpm_count(self._h, ctypes.byref(n))
+        if st != OK:
+            _raise(st, "nffacl_lpm_count")
+        return n.value
+
+    def Free(self):
+        h, self._h = getattr(self, "_h", None), None
+        if h and _lpm_free is not None:  # (None at interpreter teardown)
+            _lpm_free(h)
+
+    close = Free
+
+    def __del__(self):
+        self.Free()
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.Free()
+
+    def commit(self, device: int = 0):
+        """nffacl_lpm_commit: the current rules become the table of later lookups."""
+        st = _lpm_commit(self._h, device)
+        if st != OK:
+            _raise(st, "nffacl_lpm_commit")
+
+    def compile(self) -> np.ndarray:
+        """nffacl_lpm_compile: the device table as uint32 words, no device needed."""
+        need = _u64()
+        st = _lpm_compile(self._h, None, 0, ctypes.byref(need))
+        if st != OK:
+            _raise(st, "nffacl_lpm_compile")
+        blob = np.zeros(need.value, np.uint32)
+        st = _lpm_compile(self._h, blob.ctypes.data, len(blob), ctypes.byref(need))
+        if st != OK:
+            _raise(st, "nffacl_lpm_compile")
+        return blob
+
+    def lookup_device(self, addr, n: int, next_hop=None, hit_bits=None, flags: int = 0, miss_value: int = 0,
+                      stream=None):
+        """nffacl_lpm_lookup_device: next_hop[i] (uint32[n], optional) <- the next hop of addr[i] (uint32[n]) or
+        miss_value; bit i of hit_bits (uint64[ceil(n / 64)], optional) <- found.  Device buffers, asynchronous
+        on `stream`."""
+        s = stream.cuda_stream if hasattr(stream, "cuda_stream") else stream
+        st = _lpm_lookup(self._h, _ptr(addr), n, flags, miss_value, _ptr(next_hop), _ptr(hit_bits), s)
+        if st != OK:
+            _raise(st, "nffacl_lpm_lookup_device")
+
+    def lookup_keys_device(self, keys, n: int, next_hop=None, hit_bits=None, flags: int = 0, miss_value: int = 0,
+                           stream=None):
+        """nffacl_lpm_lookup_keys_device: the same for the destination (b) of family-4 keys (KEY_DTYPE[n]);
+        keys of another family miss."""
+        s = stream.cuda_stream if hasattr(stream, "cuda_stream") else stream
+        st = _lpm_lookup_keys(self._h, _ptr(keys), n, flags, miss_value, _ptr(next_hop), _ptr(hit_bits), s)
+        if st != OK:
+            _raise(st, "nffacl_lpm_lookup_keys_device")
+
+
+def CreateLPM(name, socket, maxRules: int, numberTbl8: int) -> LPM:
+    """CreateLPM (packet.go:868); name and socket have no meaning here."""
+    return LPM(maxRules, numberTbl8)
 
 
 ROUTE_SEPARATE, ROUTE_SPLIT = 0, 1

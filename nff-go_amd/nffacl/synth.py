@@ -493,3 +493,49 @@ def gen_l2_slots(rules: GenL2Rules, n: int, seed: int = L2_PACKET_SEED, stride: 
     buf[:, 12] = et >> 8
     buf[:, 13] = et & 0xFF
     return buf.reshape(-1)
+
+
+# ---- LPM route tables (tools/lpm_bench.py; CreateLPM, packet/packet.go:857-912) ----------
+
+LPM_ROUTE_SEED = 0x5EED0030
+LPM_ADDR_SEED = 0x9AC70030
+# depth -> share of the routes: most of a BGP table is /24, then /22-/23, /16-/21, a tail up to /32
+_LPM_BGP_MIX = {8: 0.001, 12: 0.003, 14: 0.006, 16: 0.03, 18: 0.03, 19: 0.05, 20: 0.08, 21: 0.08, 22: 0.12,
+                23: 0.09, 24: 0.46, 25: 0.01, 26: 0.01, 27: 0.008, 28: 0.008, 29: 0.006, 30: 0.004, 32: 0.004}
+
+
+def gen_lpm_routes(kind: str, seed: int = LPM_ROUTE_SEED):
+    """(ip, depth, next_hop) arrays of distinct routes, ips masked to their depth.
+    "small": 100 routes, depths uniform in 8..24, 16 next hops (the table of examples/netlink.go).
+    "large": about 500 000 routes with the depth mix above and 256 next hops, inside 150 of the unicast /8 blocks
+    (a full table leaves much of the space unrouted; 16-8-8 has a group per /16 block that holds a longer prefix)."""
+    rng = np.random.default_rng(seed + (kind == "large"))
+    if kind == "small":
+        n, depth, hops = 100, rng.integers(8, 25, 100), 16
+    elif kind == "large":
+        n, hops = 500_000, 256
+        d, p = np.array(list(_LPM_BGP_MIX)), np.array(list(_LPM_BGP_MIX.values()))
+        depth = rng.choice(d, n, p=p / p.sum())
+    else:
+        raise ValueError(kind)
+    ip = rng.integers(0, 1 << 32, n, dtype=np.uint64)
+    if kind == "large":
+        tops = rng.choice(np.arange(1, 224, dtype=np.uint64), 150, replace=False)
+        ip = tops[(ip >> np.uint64(24)) % np.uint64(150)] << np.uint64(24) | ip & np.uint64(0xFFFFFF)
+    ip &= _mask32(depth.astype(np.uint64))
+    _, first = np.unique(depth.astype(np.uint64) << 32 | ip, return_index=True)
+    first.sort()
+    return ip[first].astype(np.uint32), depth[first].astype(np.uint8), rng.integers(0, hops, n)[first].astype(np.uint32)
+
+
+def gen_lpm_addresses(routes, n: int, seed: int = LPM_ADDR_SEED, inside: float = 0.8) -> np.ndarray:
+    """n destinations (uint32, the value Lookup shifts): a fraction `inside` drawn inside a uniformly chosen
+    route, the rest uniform over the address space (which may fall into a route as well)."""
+    ip, depth, _ = routes
+    rng = np.random.default_rng(seed)
+    r = rng.integers(0, len(ip), n)
+    free = np.uint64(0xFFFFFFFF) >> depth[r].astype(np.uint64)
+    addr = rng.integers(0, 1 << 32, n, dtype=np.uint64)
+    take = rng.random(n) < inside
+    addr[take] = ip[r[take]] | (addr[take] & free[take])
+    return addr.astype(np.uint32)
