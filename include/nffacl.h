@@ -30,6 +30,9 @@
  *                                  descriptors, gathered through a route's index lists
  *   nffacl_route_gather_decap_frames_device <- the same with RemoveVLANTag / RemoveMPLS /
  *                                  DecapsulateIPv4GTP (packet.go:789-798) done on the way
+ *   nffacl_route_gather_encap_frames_device <- the same with AddVLANTag / AddMPLS /
+ *                                  EncapsulateIPv4GTP (packet.go:758-771), the next hop's MACs
+ *                                  and the TTL decrement done on the way
  *   nffacl_checksum_frames_device <- CalculateIPv4Checksum, CalculateIPv{4,6}{TCP,UDP,ICMP}Checksum
  *                                  (packet/checksum.go:186-345) over packed frames, each
  *                                  compared with the field the frame carries
@@ -916,6 +919,84 @@ NFFACL_API int nffacl_route_gather_decap_frames_device(nffacl_router *r, const u
                                                        const uint32_t *d_index, uint64_t m, uint32_t align,
                                                        uint8_t *d_out, uint64_t out_cap, uint64_t *d_out_desc,
                                                        uint64_t *d_out_bytes, void *stream);
+/* The same gather, rewriting for the next hop on the way (additive to ABI 7):
+ * what a forwarder does between the route lookup and the enqueue — the next
+ * hop's Ethernet addresses, the TTL decrement of examples/decrementTTL.go:27-40,
+ * and AddVLANTag (vlan.go:119-131), AddMPLS (mpls.go:81-91) or
+ * EncapsulateIPv4GTP (gtp.go:117-130) with the outer header fill of
+ * examples/gtpu.go:62-95, i.e. EncapsulateHead(EtherLen, length)
+ * (packet.go:758-771), which opens `length` bytes behind the Ethernet header.
+ * One nffacl_adj record describes one next hop's rewrite: */
+enum nffacl_adj_flags {
+    NFFACL_ADJ_MACS        = 1u,  /* output bytes [0,12) <- dmac, smac */
+    NFFACL_ADJ_TTL         = 2u,  /* decrement the source frame's IPv4 TTL / IPv6 hop limit (below) */
+    NFFACL_ADJ_INNER_ETYPE = 4u,  /* shim bytes [s-2, s) <- the source's bytes 12-13 (a tag's inner type, GRE NextProto); s >= 4 */
+    NFFACL_ADJ_IP4_LEN     = 8u,  /* the shim opens with a 20-byte IPv4 header: TotalLength, HdrChecksum filled; s >= 20 */
+    NFFACL_ADJ_UDP_LEN     = 16u, /* + UDP behind it: DgramLen filled; needs IP4_LEN, s >= 28 */
+    NFFACL_ADJ_GTP_LEN     = 32u  /* + GTPv1 behind that: MessageLength filled; needs UDP_LEN, s >= 36 */
+};
+typedef struct nffacl_adj {       /* 64 bytes, arrays 16-byte aligned: one next hop's rewrite */
+    uint8_t  dmac[6], smac[6];
+    uint16_t ether_type;          /* host-order number; 0 = keep the source's */
+    uint8_t  shim_len;            /* s: 0..48, a multiple of 4 */
+    uint8_t  flags;               /* nffacl_adj_flags */
+    uint8_t  shim[48];            /* template of output bytes [14, 14 + s) */
+} nffacl_adj;
+enum nffacl_rewrite_status { NFFACL_RW_APPLIED = 1u, NFFACL_RW_TTL_DONE = 2u, NFFACL_RW_TTL_EXPIRED = 4u };
+/* d_hop[0..n): one next hop per SOURCE frame — exactly the d_next that
+ * nffacl_lpm_lookup_*_device writes; only its low 24 bits are significant, as
+ * in Lookup (choose miss_value >= n_adj for "no rewrite").  d_adj[0..n_adj):
+ * device memory the caller fills, n_adj <= 2^24; may be NULL when n_adj is 0.
+ * d_status: NULL, or one byte (nffacl_rewrite_status bits) written per j < m.
+ * For output frame j: i = d_index[j]; i >= n gives the empty frame, status 0.
+ * Else L = the source length, h = d_hop[i], A = d_adj[h], s = A.shim_len.  The
+ * record APPLIES iff h < n_adj, L >= 14, s % 4 == 0, s <= 48, A.flags has no
+ * unknown bit, every flag's prerequisite above holds, and L + s <= 65535 —
+ * decided from d_desc, d_hop and the record alone, never from frame bytes.
+ * If it does not apply the frame is copied whole, bit-identical to
+ * nffacl_route_gather_frames_device, status 0.  If it applies: L' = L + s,
+ * d_out_desc[j] = off_j << 16 | L', the room is L' rounded up to `align`, pads
+ * zeroed, status has APPLIED, and the output bytes are
+ *   [0, 12)      dmac, smac under MACS, else the source's
+ *   [12, 14)     ether_type big-endian if s > 0 and ether_type != 0, else the source's
+ *   [14, 14+s)   the shim template, then in this order
+ *                  INNER_ETYPE  shim [s-2, s) <- source bytes 12-13
+ *                  GTP_LEN      shim [30, 32) <- L - 14, big-endian (gtp.go:118, 125)
+ *                  UDP_LEN      shim [24, 26) <- L' - 34; the UDP checksum stays
+ *                               what the template holds (the example sends 0)
+ *                  IP4_LEN      shim [2, 4) <- L' - 14; last, shim [10, 12) <-
+ *                               ~fold of the ten big-endian words of shim [0, 20)
+ *                               as they leave, the field taken as 0 (fold =
+ *                               reduceChecksum, checksum.go:179-184)
+ *   [14+s, L')   source bytes [14, L), under TTL with this edit:
+ *                  IPv4 (source EtherType 0x0800, version nibble at byte 14 = 4,
+ *                  IHL >= 5, L >= 34): TTL >= 2 -> TTL - 1 and HdrChecksum' =
+ *                  ~fold(~HC + ~m + m') (RFC 1624 eq. 3; m = the big-endian word
+ *                  (TTL, protocol)), status gets TTL_DONE; TTL <= 1 -> nothing
+ *                  changes, status gets TTL_EXPIRED (the frame is still
+ *                  encapsulated: the caller drops or diverts it by the status)
+ *                  IPv6 (0x86DD, nibble 6, L >= 54): the same rule on the hop
+ *                  limit (byte 21), no checksum
+ *                  anything else: neither bit
+ * A record that applies with s = 0 and flags = 0 yields the plain gather's bytes.
+ * Divergences from the reference: examples/gtpu.go:91 stores DgramLen unswapped,
+ * here every length is big-endian; decrementTTL.go leaves the header checksum
+ * to the NIC, here it is patched.
+ * Everything else — packing, align 16..4096, out_cap, *d_out_bytes, repeated
+ * indices, m <= max_n, m = 0, three launches on `stream`, no allocation, no
+ * global atomics, no memset (capturable), the router's event and one-stream
+ * rule, the scratch (nffacl_route_frames_plan), a 16-byte source chunk read
+ * only if it starts inside its frame, nothing written at or past out_cap — is
+ * as nffacl_route_gather_frames_device.  d_frames, d_out and d_adj 16-byte,
+ * d_hop 4-byte aligned.  NFFACL_ERR_INVALID_ARG, with no launch, for a bad
+ * align or out_cap, NULL or misaligned buffers, d_hop NULL with n > 0, d_adj
+ * NULL with n_adj > 0, n_adj > 2^24, m > max_n. */
+NFFACL_API int nffacl_route_gather_encap_frames_device(nffacl_router *r, const uint8_t *d_frames,
+                                                       const uint64_t *d_desc, uint64_t n, const uint32_t *d_hop,
+                                                       const nffacl_adj *d_adj, uint32_t n_adj,
+                                                       const uint32_t *d_index, uint64_t m, uint32_t align,
+                                                       uint8_t *d_out, uint64_t out_cap, uint64_t *d_out_desc,
+                                                       uint64_t *d_out_bytes, uint8_t *d_status, void *stream);
 /* Their plan (pure, no device): tiles = ceil(m / frames-per-tile);
  * scratch_bytes = what a router of max_n = m holds for this path (one 64-bit
  * sum per tile).  NFFACL_ERR_INVALID_ARG for m > 2^31 or NULL outputs. */

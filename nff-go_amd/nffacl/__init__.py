@@ -174,6 +174,8 @@ _route_gather_frames = _sig("nffacl_route_gather_frames_device", _i, _vp, _vp, _
                             _vp, _vp, _vp)
 _route_gather_decap = _sig("nffacl_route_gather_decap_frames_device", _i, _vp, _vp, _vp, _u64, _vp, _vp, _vp, _u64, _u32,
                            _vp, _u64, _vp, _vp, _vp)
+_route_gather_encap = _sig("nffacl_route_gather_encap_frames_device", _i, _vp, _vp, _vp, _u64, _vp, _vp, _u32, _vp, _u64,
+                           _u32, _vp, _u64, _vp, _vp, _vp, _vp)
 _classify_keys_device = _sig("nffacl_classify_keys_device", _i, _vp, _vp, _vp, _u32, _u64, _vp, _vp, _vp)
 _extract_keys_device = _sig("nffacl_extract_keys_device", _i, _vp, _u32, _u64, _u32, _vp, _vp, _vp)
 _extract_keys_frames = _sig("nffacl_extract_keys_frames_device", _i, _vp, _vp, _u64, _u32, _vp, _vp, _vp)
@@ -199,6 +201,12 @@ assert KEY_DTYPE.itemsize == 16 and KEY6_DTYPE.itemsize == 32
 # nffacl_cksum: one frame's checksums (host-order numbers) and CK_* status bits
 CKSUM_DTYPE = np.dtype([("ip", "<u2"), ("l4", "<u2"), ("status", "<u4")])
 assert CKSUM_DTYPE.itemsize == 8
+# nffacl_adj: one next hop's rewrite (Router.gather_encap_frames), its flags and the status bits of a rewritten frame
+ADJ_DTYPE = np.dtype([("dmac", "u1", 6), ("smac", "u1", 6), ("ether_type", "<u2"), ("shim_len", "u1"), ("flags", "u1"),
+                      ("shim", "u1", 48)])
+assert ADJ_DTYPE.itemsize == 64
+ADJ_MACS, ADJ_TTL, ADJ_INNER_ETYPE, ADJ_IP4_LEN, ADJ_UDP_LEN, ADJ_GTP_LEN = 1, 2, 4, 8, 16, 32
+RW_APPLIED, RW_TTL_DONE, RW_TTL_EXPIRED = 1, 2, 4
 
 
 class KernelInfo(ctypes.Structure):
@@ -254,6 +262,7 @@ EXPORTED_SYMBOLS = [
     "nffacl_checksum_frames_device", "nffacl_checksum_frames_plan",
     "nffacl_lpm_create", "nffacl_lpm_add", "nffacl_lpm_delete", "nffacl_lpm_count", "nffacl_lpm_free",
     "nffacl_lpm_commit", "nffacl_lpm_compile", "nffacl_lpm_lookup_device", "nffacl_lpm_lookup_keys_device",
+    "nffacl_route_gather_encap_frames_device",
 ]
 
 
@@ -830,6 +839,23 @@ class Router:
                                  align, _ptr(out), out_cap, _ptr(out_desc), _ptr(out_bytes), s)
         if st != OK:
             _raise(st, "nffacl_route_gather_decap_frames_device")
+
+    def gather_encap_frames(self, frames, desc, n: int, hop, adj, n_adj: int, index, m: int, out, out_cap: int,
+                            out_desc, out_bytes, status=None, align: int = 64, stream=None):
+        """gather_frames that rewrites each frame for its next hop on the way:
+        hop (uint32[n], what LPM.lookup_*_device wrote as next hops; low 24
+        bits) names the frame's record in adj (ADJ_DTYPE[n_adj], device memory):
+        MACs, EtherType, a shim of up to 48 bytes behind the Ethernet header
+        with its length fields and outer IPv4 checksum filled, TTL / hop limit
+        decremented and the header checksum patched (ADJ_* flags).  A hop >=
+        n_adj or a record that does not apply copies the frame whole.
+        out_desc[j] = offset << 16 | the longer length; status (uint8[m] or
+        None) <- RW_* bits per output frame.  Asynchronous on `stream`."""
+        s = stream.cuda_stream if hasattr(stream, "cuda_stream") else stream
+        st = _route_gather_encap(self._h, _ptr(frames), _ptr(desc), n, _ptr(hop), _ptr(adj), n_adj, _ptr(index), m,
+                                 align, _ptr(out), out_cap, _ptr(out_desc), _ptr(out_bytes), _ptr(status), s)
+        if st != OK:
+            _raise(st, "nffacl_route_gather_encap_frames_device")
 
 
 class Batcher:
